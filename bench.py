@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- items/s of one HiD-VAE tokenizer TRAIN step (forward + backward + grad all-reduce + AdamW) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: the script starts N rank processes itself -- or is started by torch.distributed.run --, one rank per GPU over RCCL;
      per-rank batch fixed => weak scaling)
 
@@ -9,8 +9,11 @@ Workload at N=1 = BASELINE.json configs[1]: Amazon-Beauty-shaped synthetic items
 hidden [512,256,128], D=32, 3 x 256 codebooks, ROTATION_TRICK, batch 1024 per GPU, amazon-gin hyper-parameters, WITH the tag heads
 (every h-config of the reference feeds tags: train_hidvae.py:698-709); the untagged core step is carried beside it.
 Inputs are resident in HBM before the timed region (a pool of pre-generated batches, one D2D copy per step).
-One JSON line on rank 0 carrying `roofline` (dominant kernel, timed live with HIP events) and `cpu_baseline`
-(the oracle's torch-CPU restatement of the same step, timed on this host for a bounded sample).
+A plain run sets up, warms up (W steps), times exactly K steps and prints one JSON line on rank 0 (`value`, `ms_per_step`, ...).
+--dump-outputs DIR: after the timed steps, what the last one left its caller (loss row, model state) as DIR/*.npy.
+--full: also everything that takes runs of its own: `roofline` (dominant kernel, timed live with HIP events), `kernels`, `in_step`,
+the other step variant, the large batch, BASELINE configs 3 and 5, k-means start-up, and `cpu_baseline` (the oracle's torch-CPU
+restatement of the same step, timed on this host for a bounded sample).
 """
 import argparse
 import json
@@ -42,7 +45,7 @@ MFMA_F32_PEAK_TF = 157.3   # fp32-input MFMA = vector rate
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (split into --windows windows)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=1024, help="items per GPU per step")
     ap.add_argument("--levels", type=int, default=3)
@@ -66,8 +69,17 @@ def parse():
     ap.add_argument("--time-limit", type=float, default=float(os.environ.get("HIDVAE_BENCH_TIME_LIMIT", "900")),
                     help="launcher only (--gpus N without torch.distributed.run): seconds after which the rank processes are terminated "
                          "and the launcher exits non-zero -- a rank stuck in a collective must not hold the job (0 = no limit)")
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of --steps steps each; the MEDIAN window is reported")
-    return ap.parse_args()
+    ap.add_argument("--windows", type=int, default=5, help="consecutive windows the --steps timed steps are cut into; the MEDIAN "
+                    "window's time per step is reported")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed for its "
+                    "caller (its loss row and the model state it updated) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own (roofline, kernels, in-step timeline, "
+                    "the other variant, large batch, configs 3 and 5, k-means start-up, cpu_baseline); the --also-*, --kernels and "
+                    "--cpu-seconds options select among these")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _hp(args):
@@ -502,8 +514,33 @@ def kmeans_init_times(device, budget_s=4.0):
     return out
 
 
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, m, stepper):
+    """What a caller of the timed train step holds after its last step: the step's loss row `step_losses` (total, recon, rqvae, tag
+    align, tag pred, tag accuracy) and the model's state `state.<key>` (parameters and BatchNorm buffers, which the step updates in
+    place), one .npy file each, float32 (integer counters as float64).  Above DUMP_BYTES in all, every array is cut to the same
+    fraction of its elements at fixed, seeded positions."""
+    import numpy as np
+    arrays = {"step_losses": stepper.row.detach().float().cpu().numpy()}
+    for k, v in m.state_dict().items():
+        v = v.detach().cpu()
+        arrays[f"state.{k}"] = v.numpy().astype(np.float32 if v.is_floating_point() else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        keep, rng = 0.95 * DUMP_BYTES / total, np.random.default_rng(0)
+        for k, a in arrays.items():
+            flat = a.reshape(-1)
+            arrays[k] = flat[np.sort(rng.choice(flat.size, max(1, int(flat.size * keep)), replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def run_workload(args, device, rank, world, dist):
-    """Build the model + optimizer, capture one full train step in a HIP graph, time K replays.  -> (seconds, model, info)"""
+    """Build the model + optimizer, capture one full train step in a HIP graph, time `args.steps` replays.
+    -> (seconds per step, model, info)"""
     from hidvae_amd.optim import HidvaeAdamW
     m = build_model(args, device)
     multi = dist is not None  # the data-parallel path (also taken with one rank under --dist 1)
@@ -552,15 +589,18 @@ def run_workload(args, device, rank, world, dist):
 
     for i in range(args.warmup):
         step(i)
-    # `windows` timed regions of EXACTLY `steps` steps each, every one bracketed by barrier + synchronize on both sides and reduced
-    # with MAX over ranks; the median window is the reported one (a single 5 ms sample is at the mercy of one clock ramp)
+    # EXACTLY `steps` timed steps, cut into `windows` consecutive windows of (nearly) equal size, every one bracketed by barrier +
+    # synchronize on both sides and reduced with MAX over ranks; the median window's time per step is the reported one (a single 5 ms
+    # sample is at the mercy of one clock ramp)
+    nwin = max(1, min(getattr(args, "windows", 1), args.steps))
+    sizes = [args.steps // nwin + (1 if j < args.steps % nwin else 0) for j in range(nwin)]
     windows, n = [], args.warmup
-    for _ in range(max(1, getattr(args, "windows", 1))):
+    for size in sizes:
         if multi:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for i in range(args.steps):
+        for i in range(size):
             step(n + i)
         torch.cuda.synchronize()
         if multi:
@@ -570,12 +610,12 @@ def run_workload(args, device, rank, world, dist):
             tt = torch.tensor([dt], device=device, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
-        windows.append(dt)
-        n += args.steps
-    dt = sorted(windows)[len(windows) // 2]
+        windows.append(dt / size)
+        n += size
+    sps = sorted(windows)[len(windows) // 2]
     final_loss = float(stepper.row[0]) if stepper.row is not None else float("nan")
-    return dt, m, dict(hip_graph=bool(use_graph), final_loss=final_loss, windows_ms_per_step=[w / args.steps * 1e3 for w in windows],
-                       stepper=stepper, pool_batch=pool_batch)
+    return sps, m, dict(hip_graph=bool(use_graph), final_loss=final_loss, windows_ms_per_step=[w * 1e3 for w in windows],
+                        stepper=stepper, pool_batch=pool_batch)
 
 
 
@@ -693,17 +733,19 @@ def main():
             raise RuntimeError(f"process group reports {dist.get_world_size()} ranks, the environment said {world}")
         world = dist.get_world_size()  # n_gpus of the line below = what the communicator (RCCL) reports, not what a flag asked for
 
-    dt, m, info = run_workload(args, device, rank, world, dist)
+    sps, m, info = run_workload(args, device, rank, world, dist)
+    if rank == 0 and args.dump_outputs:  # (before anything below replays the step again)
+        dump_outputs(args.dump_outputs, m, info["stepper"])
     use_graph, final_loss = info["hip_graph"], info["final_loss"]
     single = world == 1 and dist is None
     timeline = None
-    if rank == 0 and single and use_graph and args.kernels:
+    if rank == 0 and single and use_graph and args.kernels and args.full:
         timeline = step_timeline(info["stepper"], info["pool_batch"], device)
 
     def variant(vargs, label):
         """the step's other variant (or the large-batch one) as a sub-object of the line: time, launches, in-step shares, own roofline"""
-        vdt, _, vinfo = run_workload(vargs, device, rank, world, dist)
-        ex = dict(value=vargs.batch * vargs.steps / vdt, unit="items/s", ms_per_step=vdt / vargs.steps * 1e3, steps=vargs.steps,
+        vsps, _, vinfo = run_workload(vargs, device, rank, world, dist)
+        ex = dict(value=vargs.batch / vsps, unit="items/s", ms_per_step=vsps * 1e3, steps=vargs.steps,
                   batch=vargs.batch, hip_graph=vinfo["hip_graph"], windows_ms_per_step=vinfo["windows_ms_per_step"], workload=label)
         if vinfo["hip_graph"] and args.kernels and dist is None and vargs.batch <= 4096:
             vrows, _ = step_timeline(vinfo["stepper"], vinfo["pool_batch"], device)
@@ -716,7 +758,7 @@ def main():
         return ex, vargs
 
     other_extra = other_args = None
-    if single and args.also_other:
+    if single and args.full and args.also_other:
         oa = argparse.Namespace(**{**vars(args), "tagged": 0 if args.tagged else 1, "steps": max(20, args.steps // (1 if args.tagged else 4)),
                                    "warmup": max(5, args.warmup // 2)})
         other_extra, other_args = variant(oa, "untagged core step: encoder, L-level RQ, decoder, reconstruction + commitment losses (no tag heads)" if args.tagged
@@ -724,12 +766,12 @@ def main():
         if args.cpu_seconds > 0:
             other_extra["cpu_baseline"] = cpu_baseline(other_args, max(4.0, args.cpu_seconds / 2), all_cores=False)
     large_extra = None
-    if single and args.also_large and args.kernels:
+    if single and args.full and args.also_large and args.kernels:
         la = argparse.Namespace(**{**vars(args), "tagged": 0, "batch": args.also_large, "steps": max(20, args.steps // 5), "warmup": 5, "pool": 2})
         large_extra, _ = variant(la, f"untagged core step at batch {args.also_large} (the per-GPU shard of BASELINE config 4): the throughput-bound regime")
 
     config_extras = {}
-    if single and args.also_configs and args.kernels:
+    if single and args.full and args.also_configs and args.kernels:
         c3 = argparse.Namespace(**{**vars(args), "tagged": 1, "batch": 2048, "hparams": "kuairand", "levels": 3, "codes": 256,
                                    "steps": max(20, args.steps // 4), "warmup": 5, "pool": 4})
         config_extras["config3_step"], _ = variant(c3, "BASELINE config 3: KuaiRand-shaped tagged step (configs/h_rqvae_kuairand.gin hyper-parameters), "
@@ -742,16 +784,16 @@ def main():
 
     if rank == 0:
         if not args.kernels:  # profiling run of the step only (rocprofv3 timelines): no roofline object
-            print(json.dumps({"value": args.batch * world * args.steps / dt, "ms_per_step": dt / args.steps * 1e3, "note": "--kernels 0"}),
+            print(json.dumps({"value": args.batch * world / sps, "ms_per_step": sps * 1e3, "note": "--kernels 0"}),
                   flush=True)
             if dist is not None:
                 if world > 1:
                     dist.barrier()
                 dist.destroy_process_group()
             return
-        ks = kernel_rooflines(args, m, device)
-        pmc = pmc_traffic()
-        for k in ks:  # HBM-side bytes per launch from the committed rocprofv3 --pmc passes of exactly these launches (profiles/);
+        ks = kernel_rooflines(args, m, device) if args.full else None
+        pmc = pmc_traffic() if args.full else {}
+        for k in ks or []:  # HBM-side bytes per launch from the committed rocprofv3 --pmc passes of exactly these launches (profiles/);
             for key, val in pmc.items():  # a kernel whose name no longer matches a CSV row keeps traffic = null
                 if k["kernel"].startswith(key):
                     k["traffic"] = val
@@ -787,14 +829,14 @@ def main():
                                           achieved=big.get("flops", 0.0) / big["us"] * 1e-6, frac=big.get("flops", 0.0) / big["us"] * 1e-6 / MFMA_F32_PEAK_TF,
                                           traffic=warm.get("traffic") if same else None, us_warm=warm.get("us") if same else None)
             # the whole step against the fp32 MFMA peak: every GEMM-class FLOP of the step over the step's wall time
-            roof["whole_step"] = dict(flops=in_step["gemm_class"]["flops"], achieved=in_step["gemm_class"]["flops"] / (dt / args.steps) * 1e-12,
-                                      frac=in_step["gemm_class"]["flops"] / (dt / args.steps) * 1e-12 / MFMA_F32_PEAK_TF)
-        if roof is None:
+            roof["whole_step"] = dict(flops=in_step["gemm_class"]["flops"], achieved=in_step["gemm_class"]["flops"] / sps * 1e-12,
+                                      frac=in_step["gemm_class"]["flops"] / sps * 1e-12 / MFMA_F32_PEAK_TF)
+        if roof is None and ks:
             roof = dict(ks[0])
         line = {
             "metric": "item-embeddings/sec HiD-VAE train step, 768-d in, 3x256 codebooks",
-            "value": args.batch * world * args.steps / dt, "unit": "items/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "value": args.batch * world / sps, "unit": "items/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": sps * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"Amazon-Beauty-shaped synthetic 768-d, {args.levels}x{args.codes} codebooks, batch {args.batch}/GPU, "
                                    f"ROTATION_TRICK, {'tagged (projector+InfoNCE+predictor+focal/mixup: the step both h-configs run)' if args.tagged else 'untagged core'}"
@@ -807,11 +849,14 @@ def main():
                        "collectives_in_graph": bool(getattr(info["stepper"], "in_graph", False)),
                        "dp_comm": (None if info["stepper"].dp is None else
                                    "own RCCL communicator (hidvae_amd.rccl)" if getattr(info["stepper"].dp, "_comm", None) else "torch.distributed")},
-            "roofline": {k: roof[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")} | {"kernel": roof["kernel"], "us_per_launch": roof["us"]}
-                        | {k: roof[k] for k in ("share_of_step", "us_warm", "frac_warm", "largest_launch", "whole_step") if k in roof},
             "windows_ms_per_step": info["windows_ms_per_step"],
-            "kernels": ks, "final_loss": final_loss,
+            "final_loss": final_loss,
         }
+        if roof is not None:
+            line["roofline"] = ({k: roof[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")} | {"kernel": roof["kernel"], "us_per_launch": roof["us"]}
+                                | {k: roof[k] for k in ("share_of_step", "us_warm", "frac_warm", "largest_launch", "whole_step") if k in roof})
+        if ks is not None:
+            line["kernels"] = ks
         if in_step is not None:
             line["in_step"] = in_step
         if other_extra is not None:
@@ -819,7 +864,7 @@ def main():
         if large_extra is not None:
             line["large_batch_step"] = large_extra
         line.update(config_extras)
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             line["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
         degraded = bool(args.graph) and not use_graph  # the step could not be captured and ran eagerly (host-bound, ~6x slower)
         if degraded:

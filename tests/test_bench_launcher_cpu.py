@@ -104,3 +104,26 @@ def test_main_becomes_the_launcher_only_without_a_world_in_the_environment(monke
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert e.value.code == 2 and calls == []
+
+
+def test_dump_outputs_writes_the_step_results_within_the_size_limit(tmp_path, monkeypatch):
+    """--dump-outputs: the loss row and every state-dict entry as float32 (integer counters float64) .npy files; above the byte
+    budget every array is cut to a sample at fixed positions, so two runs stay comparable element for element"""
+    import types
+    import numpy as np
+    import torch
+    import bench
+    m = torch.nn.Sequential(torch.nn.Linear(300, 200), torch.nn.BatchNorm1d(200))
+    stepper = types.SimpleNamespace(row=torch.arange(6, dtype=torch.float32))
+    bench.dump_outputs(str(tmp_path / "all"), m, stepper)
+    files = {p.name: np.load(p) for p in (tmp_path / "all").iterdir()}
+    assert set(files) == {"step_losses.npy"} | {f"state.{k}.npy" for k in m.state_dict()}
+    assert files["step_losses.npy"].tolist() == list(range(6)) and files["state.0.weight.npy"].dtype == np.float32
+    assert np.array_equal(files["state.0.weight.npy"], m[0].weight.detach().numpy()) and files["state.1.num_batches_tracked.npy"].dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_BYTES", 50_000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), m, stepper)
+    a = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sum(v.nbytes for v in a.values()) <= 50_000 and set(a) == set(files)
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / k)) for k, v in a.items())
+    assert np.isin(a["state.0.weight.npy"], files["state.0.weight.npy"]).all()

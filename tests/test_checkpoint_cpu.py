@@ -3,6 +3,7 @@
 The "optimizer" entry is a genuine torch.optim.AdamW.state_dict(); the one pickled object of the file (the QuantizeForwardMode enum
 in model_config) is named by the reference's module path, so a file written here loads in an environment WITHOUT hidvae_amd and a
 file written by the reference loads here."""
+import json
 import math
 import os
 import subprocess
@@ -140,62 +141,61 @@ def test_resuming_twice_keeps_the_schedule_position():
     torch.optim.AdamW(groups_of(mirror_model())).load_state_dict(sd)  # the extra key does not disturb torch's own loader
 
 
-REFERENCE_SIDE = r'''
-import sys, types, json
-sys.path.insert(0, "/root/reference")
-g = types.ModuleType("gin"); g.configurable = lambda f=None, **k: f if f is not None else (lambda h: h); g.constants_from_enum = lambda c: c
-sys.modules["gin"] = g
+GOLDEN = os.path.join(ROOT, "tests", "golden", "checkpoint_reference_iter13.pt")
+# What the reference does with a file of ours (tests/golden/make_golden_checkpoint.py runs it and keeps what the reference wrote back):
+# torch.load in an environment without hidvae_amd (train_hidvae.py:624), HRqVae(**model_config) + a STRICT load_state_dict, its
+# AdamW groups (:533-563) + optimizer.load_state_dict (:625), the resume schedule (:638), one step on constant 1e-3 gradients, save
+# (:1161-1169).  The file it wrote holds its own state_dict and AdamW state, so the same checks need only that file.
+WITHOUT_PACKAGE = r'''
+import json, sys
 import torch
-import modules.loss as L
-L.CategoricalReconstuctionLoss = L.CategoricalReconstructionLoss
-from modules.h_rqvae import HRqVae
-from modules.quantize import QuantizeForwardMode
 assert "hidvae_amd" not in sys.modules
-src, dst = sys.argv[1], sys.argv[2]
-state = torch.load(src, map_location="cpu", weights_only=False)           # train_hidvae.py:624
-cfg = state["model_config"]
-assert cfg["codebook_mode"] is QuantizeForwardMode.ROTATION_TRICK, cfg["codebook_mode"]
-model = HRqVae(**cfg)
-model.load_state_dict(state["model"])                                      # strict: the 146-key contract, both directions
-lr, wd, pwd = 2.8e-4, 0.015, 0.02
-groups = [{"params": list(model.encoder.parameters()) + list(model.decoder.parameters()), "lr": lr, "weight_decay": wd},
-          {"params": [p for layer in model.layers for p in layer.parameters()], "lr": lr, "weight_decay": wd}]
-for i in range(cfg["n_layers"]):
-    groups.append({"params": model.tag_predictors[i].parameters(), "lr": lr * (1 + i * 0.1), "weight_decay": pwd / (1 + i * 0.2)})
-    groups.append({"params": model.tag_projectors[i].parameters(), "lr": lr * (1 + i * 0.1), "weight_decay": pwd / (1 + i * 0.2)})
-opt = torch.optim.AdamW(groups)
-opt.load_state_dict(state["optimizer"])                                    # train_hidvae.py:625
-start_iter = state["iter"] + 1
-sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=1000, eta_min=1e-6, last_epoch=start_iter - 1)   # :638
-for p in model.parameters():
-    p.grad = torch.full_like(p, 1e-3)
-opt.step(); sched.step()
-out = {"iter": start_iter, "model": model.state_dict(), "model_config": model.config, "optimizer": opt.state_dict(),
-       "accuracy": 0.7, "rqvae_loss": 0.1, "sem_id_repetition_rate": 0.01}  # :1161-1169 (config pickles the module too, SURVEY Q11)
-torch.save(out, dst)
-print("reference-side ok", len(state["model"]), float(list(opt.state.values())[0]["step"]))
+from modules.quantize import QuantizeForwardMode
+state = torch.load(sys.argv[1], map_location="cpu", weights_only=False)
+assert "hidvae_amd" not in sys.modules
+assert state["model_config"]["codebook_mode"] is QuantizeForwardMode.ROTATION_TRICK, state["model_config"]["codebook_mode"]
+print(json.dumps({"iter": state["iter"], "model": [[k, list(v.shape), str(v.dtype)] for k, v in state["model"].items()],
+                  "groups": [len(g["params"]) for g in state["optimizer"]["param_groups"]], "state": sorted(state["optimizer"]["state"])}))
 '''
+# the reference's enum (modules/quantize.py), all a file of ours needs from the reference environment to unpickle
+STAND_IN_QUANTIZE = "from enum import Enum\n\n\nclass QuantizeForwardMode(Enum):\n    GUMBEL_SOFTMAX = 1\n    STE = 2\n    ROTATION_TRICK = 3\n"
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/modules/h_rqvae.py"), reason="the reference tree only exists in the build container")
-def test_checkpoint_round_trip_through_the_reference(tmp_path):
-    from hidvae_amd.checkpoint import load_checkpoint, save_checkpoint
+def write_ours(path):
+    """-> (model, optimizer) of the checkpoint written to `path` (iter 12, seeded Adam moments)"""
+    from hidvae_amd.checkpoint import save_checkpoint
     m = mirror_model()
     opt = HidvaeAdamW(groups_of(m), cosine=(1000, 1e-6)).prepare()
     g = torch.Generator().manual_seed(1)
     opt._m.copy_(torch.randn(opt._m.shape, generator=g) * 1e-3)
     opt._v.copy_(torch.rand(opt._v.shape, generator=g) * 1e-6)
     opt.step_dev[0] = 12
-    ours, theirs = str(tmp_path / "ours.pt"), str(tmp_path / "theirs.pt")
     save_checkpoint({"iter": 12, "model": m.state_dict(), "model_config": m.config, "optimizer": opt.state_dict(), "accuracy": 0.65,
-                     "rqvae_loss": 0.2, "sem_id_repetition_rate": 0.02}, ours)
+                     "rqvae_loss": 0.2, "sem_id_repetition_rate": 0.02}, path)
+    return m, opt
+
+
+def test_checkpoint_round_trip_through_the_reference(tmp_path):
+    from hidvae_amd.checkpoint import load_checkpoint
+    ours = str(tmp_path / "ours.pt")
+    m, opt = write_ours(ours)
     from hidvae_amd.modules.quantize import QuantizeForwardMode
     assert QuantizeForwardMode.__module__ == "hidvae_amd.modules.quantize" and "modules.quantize" not in sys.modules  # aliases were temporary
-    env = {**os.environ, "TORCHDYNAMO_DISABLE": "1"}
-    out = subprocess.run([sys.executable, "-c", REFERENCE_SIDE, ours, theirs], capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
-    assert out.returncode == 0 and "reference-side ok" in out.stdout, out.stderr[-3000:]
-    # the file the REFERENCE wrote (its own torch optimizer, its own pickled enum and module) loads here
-    state = load_checkpoint(theirs, map_location="cpu")
+    # our file in an environment WITHOUT hidvae_amd, where modules.quantize is the reference's
+    (tmp_path / "modules").mkdir()
+    (tmp_path / "modules" / "__init__.py").write_text("")
+    (tmp_path / "modules" / "quantize.py").write_text(STAND_IN_QUANTIZE)
+    env = {**os.environ, "TORCHDYNAMO_DISABLE": "1", "PYTHONPATH": str(tmp_path)}
+    out = subprocess.run([sys.executable, "-c", WITHOUT_PACKAGE, ours], capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
+    assert out.returncode == 0, out.stderr[-3000:]
+    seen = json.loads(out.stdout.strip().splitlines()[-1])
+    # the file the REFERENCE wrote back from the same file of ours (its own torch optimizer, its own pickled enum and module) loads here
+    state = load_checkpoint(GOLDEN, map_location="cpu")
+    # the reference's strict load_state_dict and AdamW.load_state_dict accept exactly its own keys, shapes and group sizes
+    assert seen["iter"] == 12
+    assert seen["model"] == [[k, list(v.shape), str(v.dtype)] for k, v in state["model"].items()]
+    assert seen["groups"] == [len(g["params"]) for g in state["optimizer"]["param_groups"]]
+    assert seen["state"] == list(range(sum(seen["groups"])))
     assert state["iter"] == 13 and state["model_config"]["codebook_mode"] is QuantizeForwardMode.ROTATION_TRICK
     assert "self" not in state["model_config"]
     m2 = mirror_model()
@@ -207,4 +207,3 @@ def test_checkpoint_round_trip_through_the_reference(tmp_path):
     # one torch AdamW step on constant gradients from our moments: m' = 0.9 m + 0.1 g, v' = 0.999 v + 0.001 g^2
     assert torch.allclose(opt2._m, 0.9 * opt._m + 0.1 * 1e-3, rtol=1e-5, atol=1e-9)
     assert torch.allclose(opt2._v, 0.999 * opt._v + 0.001 * 1e-6, rtol=1e-5, atol=1e-12)
-

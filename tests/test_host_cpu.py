@@ -7,6 +7,8 @@ import torch
 import hidvae_amd  # noqa: F401
 from hidvae_amd import gin_compat as gin
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
 CONFIG = '''
 import data.tags_processed
 import modules.quantize
@@ -47,14 +49,14 @@ def test_gin_subset_parser_binds_train_arguments():
     gin.clear_config()
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/configs"), reason="reference configs only exist in the build container")
 @pytest.mark.parametrize("cfg", ["h_rqvae_amazon.gin", "h_rqvae_kuairand.gin"])
 def test_reference_gin_files_parse(cfg):
-    """Every binding of the two tokenizer configs is accepted and names an argument of train()."""
+    """Every binding of the two tokenizer configs (the reference's configs/*.gin, kept in tests/golden/) is accepted and names an
+    argument of train()."""
     import inspect
     from hidvae_amd.train_hidvae import train
     gin.clear_config()
-    gin.parse_config_file(os.path.join("/root/reference/configs", cfg),
+    gin.parse_config_file(os.path.join(GOLDEN, cfg),
                           import_aliases={"data.tags_processed": "hidvae_amd.data.items", "modules.quantize": "hidvae_amd.modules.quantize"})
     b = gin.bindings("train")
     params = set(inspect.signature(train.__wrapped__).parameters)
@@ -109,29 +111,44 @@ def test_install_dropin_aliases_reference_module_names():
     assert out.returncode == 0 and "ok" in out.stdout, out.stderr[-2000:]
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/modules/utils.py"), reason="the reference tree only exists in the build container")
-def test_install_dropin_keeps_unmirrored_reference_modules_importable():
+# The reference's package layout (its tree as far as these tests import it): un-mirrored modules with the names the stand-in
+# tree must provide, and the leaves install_dropin() mirrors.  A stand-in of a mirrored leaf refuses to be imported.
+STAND_IN_TREE = {"modules/utils.py": ["parse_config"], "modules/transformer/attention.py": [], "modules/embedding/id_embedder.py": [],
+                 "data/tags_processed.py": [], "data/utils.py": None, "data/schemas.py": None, "modules/h_rqvae.py": None,
+                 "modules/rqvae.py": None, "modules/encoder.py": None, "modules/quantize.py": None, "modules/loss.py": None,
+                 "modules/normalize.py": None, "modules/tokenizer/h_semids.py": None, "init/kmeans.py": None,
+                 "distributions/gumbel.py": None, "ops/triton/jagged.py": None}
+
+
+def test_install_dropin_keeps_unmirrored_reference_modules_importable(tmp_path):
     """install_dropin() replaces LEAF modules only: the reference's own packages stay in place, so the import block of its
     train_hidvae.py (`from modules.utils import parse_config`, line 9) and the stage-2 modules still resolve to its files, while the
-    mirrored names resolve to the HIP implementation.  (`gin` is not installed here: a decorator stub stands in, as in
-    tests/golden/make_golden.py.)"""
+    mirrored names resolve to the HIP implementation -- here on a stand-in of the reference's tree with the same package layout."""
     import subprocess
     import sys
-    code = ("import sys, types; sys.path.insert(0, %r); sys.path.insert(0, '/root/reference'); "
-            "g = types.ModuleType('gin'); g.configurable = lambda f=None, **k: f if f is not None else (lambda h: h); "
-            "g.constants_from_enum = lambda c: c; g.parse_config_file = lambda *a, **k: None; sys.modules['gin'] = g; "
+    for rel, names in STAND_IN_TREE.items():
+        path = tmp_path.joinpath(*rel.split("/"))
+        for d in [p for p in path.parents if p != tmp_path and tmp_path in p.parents]:
+            d.mkdir(parents=True, exist_ok=True)
+            d.joinpath("__init__.py").touch()
+        body = "".join(f"def {n}(*a, **k):\n    pass\n" for n in names) if names is not None else \
+            f"raise ImportError('{rel}: the reference tree\\'s own file of a mirrored module was imported')\n"
+        path.write_text(body)
+    tree = str(tmp_path)
+    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r); "
             "import hidvae_amd; hidvae_amd.install_dropin(); "
             "import modules, modules.utils, modules.transformer.attention, modules.embedding.id_embedder; "
             "from modules.utils import parse_config; "
-            "assert modules.__file__.startswith('/root/reference') and modules.utils.__file__.startswith('/root/reference'); "
+            "assert modules.__file__.startswith(%r) and modules.utils.__file__.startswith(%r); "
             "from modules.h_rqvae import HRqVae; from modules.quantize import QuantizeForwardMode; "
             "from modules.tokenizer.h_semids import HSemanticIdTokenizer; from data.utils import batch_to, cycle, next_batch; "
             "from distributions.gumbel import TemperatureScheduler, gumbel_softmax_sample; from modules.loss import ReconstructionLoss; "
             "import modules.h_rqvae; assert modules.h_rqvae is sys.modules['modules.h_rqvae']; "
             "assert HRqVae.__module__ == 'hidvae_amd.modules.h_rqvae' and HSemanticIdTokenizer.__module__.startswith('hidvae_amd.'); "
             "assert gumbel_softmax_sample.__module__ == 'hidvae_amd.distributions.gumbel'; "
-            "assert ReconstructionLoss.__module__ == 'hidvae_amd.modules.loss'; print('ok')"
-            % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+            "assert ReconstructionLoss.__module__ == 'hidvae_amd.modules.loss'; "
+            "import data.tags_processed; assert data.tags_processed.__file__.startswith(%r); print('ok')"
+            % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), tree, tree, tree, tree))
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=180)
     assert out.returncode == 0 and "ok" in out.stdout, out.stderr[-2000:]
 

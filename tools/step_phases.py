@@ -31,7 +31,7 @@ def main():
     torch.cuda.set_device(0)
     device = torch.device("cuda", 0)
     a = argparse.Namespace(**{**vars(args), "steps": 20, "warmup": 5, "graph": 1, "dist": 0, "windows": 1})
-    dt, _, info = bench.run_workload(a, device, 0, 1, None)
+    sps, _, info = bench.run_workload(a, device, 0, 1, None)
     stepper, pool_batch = info["stepper"], info["pool_batch"]
     stepper.graphs = None
     marks = _C.phases_begin(device)
@@ -48,7 +48,7 @@ def main():
     streams = {}
     for _, st, _ in runs[0]:
         streams.setdefault(st, len(streams))
-    print(f"# {'tagged' if args.tagged else 'untagged'} step B={args.batch} {args.levels}x{args.codes}: un-marked step {dt / a.steps * 1e3:.4f} ms; "
+    print(f"# {'tagged' if args.tagged else 'untagged'} step B={args.batch} {args.levels}x{args.codes}: un-marked step {sps * 1e3:.4f} ms; "
           f"{len(runs[0])} marks, median over {len(runs)} replays")
     med = [(lab, streams[st], statistics.median(r[i][2] for r in runs)) for i, (lab, st, _) in enumerate(runs[0])]
     for lab, lane, t in sorted(med, key=lambda r: r[2]):

@@ -28,8 +28,8 @@ def timeline(args, device):
 
 def plain_step_ms(args, device, steps=100):
     a = argparse.Namespace(**{**vars(args), "steps": steps, "warmup": 10, "graph": 1, "dist": 0, "windows": 3})
-    dt, _, _ = bench.run_workload(a, device, 0, 1, None)
-    return dt / steps * 1e3
+    sps, _, _ = bench.run_workload(a, device, 0, 1, None)
+    return sps * 1e3
 
 
 def main():

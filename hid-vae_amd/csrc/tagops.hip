@@ -740,7 +740,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float *x, int64_t l
     }
 }
 
-// backward: partial (sum gh*xhat, sum gh) per (64 columns x 64 rows), then every workgroup adds the chunks of its columns in
+// backward: partial (sum gh*xhat, sum gh) per (64 columns x 32 rows), then every workgroup adds the chunks of its columns in
 // ascending order and writes gx for 16 rows
 constexpr int BN2_BWD_ROWS = 32;  // rows per partial chunk of the backward: every load of a thread's 8 rows is in flight at once (64-row
                                   // chunks walked four rows at a time: 14.2 us in the step at 1024 x 512)

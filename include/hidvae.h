@@ -448,8 +448,9 @@ int hidvae_gate_bwd(const float *gh, int64_t ldgh, const float *x, int64_t ldx, 
 /* BatchNorm1d (h_rqvae.py:325): y = dropout(relu?(BN(x))).  training != 0: batch statistics (biased variance for the
  * normalisation, unbiased for the running update with `momentum`), saved mean / rstd for the backward;
  * training == 0: running statistics.  num_batches_tracked (optional int64 device scalar) is incremented in training.
- * workspace (3*ceil(M/64)*N floats forward, 2*ceil(M/64)*N backward): selects the row-parallel form (per-chunk statistics merged
- * with Chan's update in ascending chunk order, then a row-parallel apply launch); NULL: one workgroup per 32 columns. */
+ * workspace (3*ceil(M/64)*N floats forward, 2*ceil(M/32)*N backward): selects the row-parallel form (per-chunk statistics merged
+ * with Chan's update in ascending chunk order, then a row-parallel apply launch); NULL: one workgroup per 32 columns (training only:
+ * evaluation always takes the row-parallel apply, which needs no workspace). */
 int hidvae_batchnorm_fwd(const float *x, int64_t ldx, int64_t M, int64_t N, const float *gamma, const float *beta, float eps,
                          float momentum, int training, float *running_mean, float *running_var,
                          int64_t *num_batches_tracked, float *y, float *save_mean, float *save_rstd, int relu,

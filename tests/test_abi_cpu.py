@@ -59,3 +59,26 @@ def test_query_workspace_is_host_only_and_matches_the_documented_formulas():
         q(99, 1)
     with pytest.raises(RuntimeError):
         q(_C.WS_GEMM, 1, 2)  # too few dimensions
+
+
+def _kernel_constant(name):
+    text = open(os.path.join(ROOT, "hid-vae_amd", "csrc", "tagops.hip")).read()
+    return int(re.search(rf"constexpr int {name} = (\d+);", text).group(1))
+
+
+@pytest.mark.parametrize("M", [1, 33, 65, 1000, 4097])
+def test_query_workspace_follows_the_kernels_row_chunks_at_ragged_sizes(M):
+    """The row-parallel BatchNorm writes 3 floats (count, mean, M2) per column per chunk of BN2_ROWS rows forward and 2 (sum gh*xhat,
+    sum gh) per chunk of BN2_BWD_ROWS rows backward; the tag loss one row_loss, one row_hit and a C-float scratch row per item.  The
+    sizes hidvae_query_workspace reports, and the ones include/hidvae.h documents, are those at every M, not only at multiples."""
+    from hidvae_amd import _C
+    fwd_rows, bwd_rows = _kernel_constant("BN2_ROWS"), _kernel_constant("BN2_BWD_ROWS")
+    assert (fwd_rows, bwd_rows) == (64, 32)
+    cdiv = lambda a, b: -(-a // b)
+    for N in (1, 63, 65, 768):
+        assert _C.workspace_bytes(_C.WS_BATCHNORM_FWD, M, N) == 3 * cdiv(M, fwd_rows) * N * 4
+        assert _C.workspace_bytes(_C.WS_BATCHNORM_BWD, M, N) == 2 * cdiv(M, bwd_rows) * N * 4
+    for C in (1, 38, 513, 2053):
+        assert _C.workspace_bytes(_C.WS_TAG_LOSS, M, C) == (2 * M + M * C) * 4
+    header = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "hidvae.h")).read())
+    assert f"workspace (3*ceil(M/{fwd_rows})*N floats forward, 2*ceil(M/{bwd_rows})*N backward)" in header

@@ -91,9 +91,14 @@ _SIGNATURES = {
     "hidvae_softmax_argmax_rows": [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp],
     "hidvae_timestamp": [_vp, _vp],
     "hidvae_linear_bwd_group": [_vp, _i, _vp],
+    "hidvae_gemm_bf16": [_i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _vp, _i64, _vp, _i64, _f, _vp, _u32, _u32, _vp, _i, _vp],
+    "hidvae_linear_bwd_bf16": [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i, _vp, _i64, _i, _vp, _i64, _f, _vp, _i, _vp, _vp],
+    "hidvae_linear_bwd_group_bf16": [_vp, _i, _vp],
 }
 WS_GEMM, WS_LINEAR_BWD, WS_COLSUM, WS_CODEBOOK_GRAD, WS_LAYERNORM_PARAM_GRAD, WS_LAYERNORM_BWD_ALL = 1, 2, 3, 4, 5, 6
 WS_BATCHNORM_FWD, WS_BATCHNORM_BWD, WS_ID_CENSUS, WS_KMEANS, WS_TAG_LOSS, WS_LINEAR_BWD_ZEROED, WS_RQ_FORWARD = 7, 8, 9, 10, 11, 12, 13
+WS_LINEAR_BWD_BF16, WS_GEMM_BF16, WS_BF16_ZEROED = 14, 15, 16
+PRECISIONS = ("fp32", "bf16")  # operand precision of the Linear entry points (bf16: the amp mode's kernels)
 
 
 class LaunchStamps:
@@ -211,7 +216,9 @@ def _gemm_dims(name, a):
     """(M, N, K, flops) of a GEMM-class launch from its C arguments (for the in-step roofline rows of bench.py)"""
     if name == "hidvae_gemm_f32":
         return (int(a[1]), int(a[2]), int(a[3]), 2.0 * a[1] * a[2] * a[3])
-    if name == "hidvae_linear_bwd":  # dW = g^T x (always) + dX = g W (when dX != NULL)
+    if name == "hidvae_gemm_bf16":
+        return (int(a[0]), int(a[1]), int(a[2]), 2.0 * a[0] * a[1] * a[2])
+    if name in ("hidvae_linear_bwd", "hidvae_linear_bwd_bf16"):  # dW = g^T x (always) + dX = g W (when dX != NULL)
         B, n_out, n_in = int(a[6]), int(a[7]), int(a[8])
         return (B, n_out, n_in, (4.0 if a[12] is not None else 2.0) * B * n_out * n_in)
     if name == "hidvae_bottleneck_fwd":  # enc[-2:] + L levels of K codes + dec[:2] on B items (see include/hidvae.h for the argument order)
@@ -428,10 +435,22 @@ def dropout_mask(spec, shape):
     return out
 
 
+def _precision(precision):
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision={precision!r}: expected one of {PRECISIONS}")
+    return precision == "bf16"
+
+
 def gemm(layout, A, B, out=None, bias=None, epilogue=EPI_NONE, aux=None, split_k=1, accumulate=False, mask=None,
-         mask_scale=1.0):
-    """C = epilogue(op(A) op(B) + bias).  NT: A[M,K] B[N,K]; NN: A[M,K] B[K,N]; TN: A[K,M] B[K,N]."""
+         mask_scale=1.0, precision="fp32"):
+    """C = epilogue(op(A) op(B) + bias).  NT: A[M,K] B[N,K]; NN: A[M,K] B[K,N]; TN: A[K,M] B[K,N].
+    precision="bf16": operands rounded to bf16 where they are read, fp32 accumulation and epilogue (hidvae_gemm_bf16; NT only, split_k
+    does not apply)."""
     _f32(A, "A"), _f32(B, "B")
+    if _precision(precision):
+        if layout != GEMM_NT:
+            raise NotImplementedError("gemm(precision='bf16') is the forward NT product only (the backward: linear_bwd)")
+        return _gemm_bf16(A, B, out, bias, epilogue, aux, accumulate, mask, mask_scale)
     lda, ldb = _row_stride(A, "A"), _row_stride(B, "B")
     if layout == GEMM_NT:
         M, K = A.shape
@@ -456,10 +475,32 @@ def gemm(layout, A, B, out=None, bias=None, epilogue=EPI_NONE, aux=None, split_k
     return out
 
 
+def _gemm_bf16(A, B, out, bias, epilogue, aux, accumulate, mask, mask_scale):
+    M, K = A.shape
+    N, K2 = B.shape
+    if K != K2:
+        raise RuntimeError(f"gemm: inner dimensions differ ({K} vs {K2})")
+    if out is None:
+        out = torch.empty((M, N), device=A.device, dtype=torch.float32)
+    ws = _lane_ws(A.device, workspace_bytes(WS_GEMM_BF16, M, N, K))  # arrival counters at its head: one buffer per stream
+    ldaux = _row_stride(aux, "aux") if aux is not None else 0
+    mp, rs, site, thr = _mask_args(mask)
+    ldmask = _row_stride(mask, "mask") if mp is not None else 0
+    rc = lib().hidvae_gemm_bf16(M, N, K, _p(A), _row_stride(A, "A"), _p(B), _row_stride(B, "B"), _p(bias), _p(out), _row_stride(out, "C"),
+                                epilogue, _p(aux), ldaux, mp, ldmask, float(mask_scale), rs, site, thr, _p(ws), int(accumulate), _stream())
+    if rc != 0:
+        msg = lib().hidvae_last_error().decode()
+        reset_lane_workspaces()
+        raise RuntimeError(f"hidvae_gemm_bf16 failed ({rc}): {msg}")
+    return out
+
+
 def linear_bwd(g, x, w, need_dx=True, epilogue=EPI_NONE, aux=None, dW=None, accumulate=False, bias=False, db=None, accumulate_db=False,
-               dx_scale=1.0):
+               dx_scale=1.0, precision="fp32"):
     """backward of y = x W^T in one launch -> (dW [n_out,n_in], dX [B,n_in] or None); dX = epilogue(g W) with a D* code + aux.
-    dx_scale multiplies the EPI_DRELU result: the backward through ReLU -> Dropout(keep_scale) read off that layer's saved output."""
+    dx_scale multiplies the EPI_DRELU result: the backward through ReLU -> Dropout(keep_scale) read off that layer's saved output.
+    precision="bf16": g, x and W rounded to bf16 where they are read (hidvae_linear_bwd_bf16), everything else as fp32."""
+    bf16 = _precision(precision)
     _f32(g, "g"), _f32(x, "x")
     B, n_out = g.shape
     n_in = x.shape[1]
@@ -474,19 +515,26 @@ def linear_bwd(g, x, w, need_dx=True, epilogue=EPI_NONE, aux=None, dW=None, accu
     if bias and db is None:
         db = torch.empty((n_out,), device=g.device, dtype=torch.float32)
         accumulate_db = False
-    if workspace_bytes(WS_LINEAR_BWD_ZEROED, B, n_out, n_in, int(bool(bias))):
-        ws = _lane_ws(g.device, workspace_bytes(WS_LINEAR_BWD, B, n_out, n_in, int(bool(bias))))
+    if bf16:
+        ws = _lane_ws(g.device, workspace_bytes(WS_LINEAR_BWD_BF16, B, n_out, n_in, int(bool(bias))))
+        rc = lib().hidvae_linear_bwd_bf16(_p(g), _row_stride(g, "g"), _p(x), _row_stride(x, "x"), _p(w if need_dx else None),
+                                          _row_stride(w, "W") if need_dx else 0, B, n_out, n_in, _p(dW), n_in, int(bool(accumulate)), _p(dX),
+                                          n_in, int(epilogue), _p(aux), _row_stride(aux, "aux") if aux is not None else 0, float(dx_scale),
+                                          _p(db if bias else None), int(bool(accumulate_db)), _p(ws), _stream())
     else:
-        ws = _ws(WS_LINEAR_BWD, g.device, B, n_out, n_in, int(bool(bias)))
-    rc = lib().hidvae_linear_bwd(_p(g), _row_stride(g, "g"), _p(x), _row_stride(x, "x"), _p(w if need_dx else None),
-                                 _row_stride(w, "W") if need_dx else 0, B, n_out, n_in, _p(dW), n_in, int(bool(accumulate)), _p(dX), n_in,
-                                 int(epilogue), _p(aux), _row_stride(aux, "aux") if aux is not None else 0, float(dx_scale),
-                                 _p(db if bias else None), int(bool(accumulate_db)), _p(ws),
-                                 int(int(torch.cuda.current_stream(g.device).cuda_stream) in _SIDE_STREAMS), _stream())
+        if workspace_bytes(WS_LINEAR_BWD_ZEROED, B, n_out, n_in, int(bool(bias))):
+            ws = _lane_ws(g.device, workspace_bytes(WS_LINEAR_BWD, B, n_out, n_in, int(bool(bias))))
+        else:
+            ws = _ws(WS_LINEAR_BWD, g.device, B, n_out, n_in, int(bool(bias)))
+        rc = lib().hidvae_linear_bwd(_p(g), _row_stride(g, "g"), _p(x), _row_stride(x, "x"), _p(w if need_dx else None),
+                                     _row_stride(w, "W") if need_dx else 0, B, n_out, n_in, _p(dW), n_in, int(bool(accumulate)), _p(dX), n_in,
+                                     int(epilogue), _p(aux), _row_stride(aux, "aux") if aux is not None else 0, float(dx_scale),
+                                     _p(db if bias else None), int(bool(accumulate_db)), _p(ws),
+                                     int(int(torch.cuda.current_stream(g.device).cuda_stream) in _SIDE_STREAMS), _stream())
     if rc != 0:
         msg = lib().hidvae_last_error().decode()
         reset_lane_workspaces()  # the zero-on-entry contract of the arrival counters may no longer hold
-        raise RuntimeError(f"hidvae_linear_bwd failed ({rc}): {msg}")
+        raise RuntimeError(f"hidvae_linear_bwd{'_bf16' if bf16 else ''} failed ({rc}): {msg}")
     if bias:
         return dW, dX, db
     return dW, dX
@@ -1224,9 +1272,12 @@ def _dp(t):
     return t.data_ptr() if t is not None else None
 
 
-def linear_bwd_group(problems):
+def linear_bwd_group(problems, precision="fp32"):
     """problems: list of dicts with the arguments of linear_bwd() (g, x, w, need_dx, epilogue, aux, dW, accumulate, bias, db,
-    accumulate_db); ONE launch for every dW, dX and db of the group.  -> list of (dW, dX or None, db or None)"""
+    accumulate_db); ONE launch for every dW, dX and db of the group.  -> list of (dW, dX or None, db or None)
+    precision="bf16": hidvae_linear_bwd_group_bf16 (one bf16 ring launch per problem, bit-identical to linear_bwd(precision="bf16"))"""
+    bf16 = _precision(precision)
+    lane = _lane_ws(problems[0]["g"].device, workspace_bytes(WS_LINEAR_BWD_BF16, 1, 1, 1, 1)) if bf16 and problems else None
     arr = (LinearBwdProblem * len(problems))()
     outs, keep = [], []
     for q, pr in zip(arr, problems):
@@ -1245,7 +1296,7 @@ def linear_bwd_group(problems):
         if pr.get("bias") and db is None:
             db, accb = torch.empty((n_out,), device=g.device, dtype=torch.float32), False
         aux = pr.get("aux")
-        ws = _ws(WS_LINEAR_BWD, g.device, B, n_out, n_in, int(db is not None))
+        ws = lane if bf16 else _ws(WS_LINEAR_BWD, g.device, B, n_out, n_in, int(db is not None))
         q.g, q.ldg, q.x, q.ldx = g.data_ptr(), _row_stride(g, "g"), x.data_ptr(), _row_stride(x, "x")
         q.W, q.ldw = (w.data_ptr(), _row_stride(w, "W")) if need_dx else (None, 0)
         q.B, q.n_out, q.n_in = B, n_out, n_in
@@ -1255,6 +1306,13 @@ def linear_bwd_group(problems):
         q.db, q.accumulate_db, q.workspace = _dp(db), int(accb), _dp(ws)
         outs.append((dW, dX, db))
         keep.append(ws)
+    if bf16:
+        rc = lib().hidvae_linear_bwd_group_bf16(ctypes.cast(arr, _vp), len(problems), _stream())
+        if rc != 0:
+            msg = lib().hidvae_last_error().decode()
+            reset_lane_workspaces()
+            raise RuntimeError(f"hidvae_linear_bwd_group_bf16 failed ({rc}): {msg}")
+        return outs
     _check(lib().hidvae_linear_bwd_group(ctypes.cast(arr, _vp), len(problems), _stream()), "hidvae_linear_bwd_group")
     return outs
 

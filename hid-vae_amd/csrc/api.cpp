@@ -46,6 +46,9 @@ extern "C" int hidvae_query_workspace(int op, const int64_t *d, int n, int64_t *
     case HIDVAE_WS_LINEAR_BWD_ZEROED:  // B, n_out, n_in, has_bias: leading bytes that must be zero on entry (and are zero on return)
         if (need(3)) fl = hv_lbwd_balanced(d[0], d[1], d[2]) ? HV_SK_COUNTERS : 0;
         break;
+    case HIDVAE_WS_LINEAR_BWD_BF16: if (need(4)) fl = HV_SK_WS_FLOATS; break;                         // B, n_out, n_in, has_bias
+    case HIDVAE_WS_GEMM_BF16: if (need(3)) fl = HV_SK_WS_FLOATS; break;                               // M, N, K
+    case HIDVAE_WS_BF16_ZEROED: fl = HV_SK_COUNTERS; break;                                           // (any)
     case HIDVAE_WS_COLSUM: if (need(2)) fl = cdiv(d[0], 64) * d[1]; break;                             // M, N
     case HIDVAE_WS_CODEBOOK_GRAD: if (need(3)) fl = d[0] > 2048 ? d[1] * d[2] * cdiv(d[0], 2048) * 32 : 0; break;  // B, L, K  (the slabbed form belongs to the 32-wide kernels)
     case HIDVAE_WS_LAYERNORM_PARAM_GRAD: if (need(2)) fl = 2 * cdiv(d[0], 128) * d[1]; break;          // M, N

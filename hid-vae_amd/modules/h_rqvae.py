@@ -344,8 +344,47 @@ class HRqVae(nn.Module, _HubMixin):
         cb, cc = _C.codebook_prepare([t.detach() for t in self._tables()], self._normalize_flags())
         return _C.rq_ids(y, cb, cc, False)
 
+    # ------------------------------------------------------------------------------------------ amp
+    def amp_bf16_parameters(self) -> List[str]:
+        """State-dict names of the weights whose Linear layers take bf16 operands (fp32 accumulation and storage) when the forward runs
+        under torch.autocast("cuda", dtype=torch.bfloat16) -- the amp mode, DESIGN.md 4.5.  Fixed for the model, whatever the batch
+        size: the encoder's layers but its last two, the decoder's but its first two (the four around the bottleneck stay fp32, fused
+        or not), every Linear of the tag projectors, and the tag predictors of levels >= 1 behind their gate when a layer of theirs is
+        wider than the one-launch predictor takes (those always run layer by layer).  Everything else stays fp32: the gate, level 0's
+        predictor, the quantiser, InfoNCE, the norms and the losses."""
+        def linears(seq, prefix):
+            return [f"{prefix}.{k}.weight" for k, m in enumerate(seq) if isinstance(m, nn.Linear)]
+        names = linears(self.encoder.mlp, "encoder.mlp")[:-2] + linears(self.decoder.mlp, "decoder.mlp")[2:]
+        for i, proj in enumerate(self.tag_projectors):
+            names += linears(proj, f"tag_projectors.{i}")
+        for i, pred in enumerate(self.tag_predictors):
+            lins = [(n, m) for n, m in pred.named_modules() if isinstance(m, nn.Linear) and not n.startswith("attention.")]
+            if i >= 1 and max(max(m.in_features, m.out_features) for _, m in lins) > _C.PRED_WMAX:
+                names += [f"tag_predictors.{i}.{n}.weight" for n, _ in lins]
+        return names
+
+    def _mark_amp_parameters(self):
+        """tag each Parameter with its amp policy (ops.precision_of reads it); redone per amp forward, so a load_pretrained that
+        rebuilt the heads is followed"""
+        listed = set(self.amp_bf16_parameters())
+        for n, p in self.named_parameters():
+            p._hv_amp_bf16 = n in listed
+
     # ------------------------------------------------------------------------------------------ the step
     def forward(self, batch, gumbel_t: float = 1.0) -> HRqVaeComputedLosses:
+        """the training / eval step.  Under torch.autocast("cuda", dtype=torch.bfloat16) (what the reference's accelerator.autocast()
+        sets up) the layers of amp_bf16_parameters() take bf16 operands; torch's own autocast is off inside, so every tensor of the step
+        stays fp32.  Autocast with float16 computes in fp32, after a warning."""
+        if not torch.is_autocast_enabled("cuda"):
+            return self._forward(batch, gumbel_t)
+        from ..ops import amp_scope, autocast_wants_bf16
+        bf16 = autocast_wants_bf16()
+        if bf16:
+            self._mark_amp_parameters()
+        with amp_scope(bf16):
+            return self._forward(batch, gumbel_t)
+
+    def _forward(self, batch, gumbel_t: float = 1.0) -> HRqVaeComputedLosses:
         x = batch.x.float().contiguous()
         tags_emb = getattr(batch, "tags_emb", None)
         tags_indices = getattr(batch, "tags_indices", None)

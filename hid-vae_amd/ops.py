@@ -1,12 +1,54 @@
 """Autograd operators of the tokenizer step: each forward/backward is one or a few C-ABI launches (_C.py).
 
 No torch arithmetic runs on the hot path: torch supplies device memory, streams and the autograd tape only."""
+import contextlib
 import os
+import threading
+import warnings
 
 import torch
 from torch.autograd import Function
 
 from . import _C
+
+
+# ---- amp: bf16 operands, fp32 accumulation and storage, on the Linear layers a model lists (HRqVae.amp_bf16_parameters
+# marks each such Parameter with `_hv_amp_bf16`).  The model's forward decides once, from torch.autocast, and runs its body inside
+# amp_scope(): there torch's own autocast is off (no host-side torch op of the port makes a bf16 tensor) and every Linear autograd
+# Function below looks its weight up with precision_of() and records the answer in ctx for its backward, which runs outside autocast.
+class _AmpState(threading.local):
+    bf16 = False
+
+
+_AMP = _AmpState()
+
+
+def autocast_wants_bf16(device_type="cuda"):
+    """True when torch.autocast is active with bfloat16.  Autocast with another dtype (float16) computes in fp32 as without it, after
+    a warning: fp16 needs dynamic loss scaling, which the early per-level AdamW of the step cannot take."""
+    if not torch.is_autocast_enabled(device_type):
+        return False
+    dt = torch.get_autocast_dtype(device_type)
+    if dt == torch.bfloat16:
+        return True
+    warnings.warn(f"autocast with {dt} is not supported by the HIP path (only bfloat16): computing in fp32", UserWarning, stacklevel=3)
+    return False
+
+
+@contextlib.contextmanager
+def amp_scope(bf16):
+    prev = _AMP.bf16
+    _AMP.bf16 = bool(bf16)
+    try:
+        with torch.autocast("cuda", enabled=False):
+            yield
+    finally:
+        _AMP.bf16 = prev
+
+
+def precision_of(w):
+    """operand precision of the Linear layer with weight w in the running forward: "bf16" inside a bf16 amp_scope for a listed weight"""
+    return "bf16" if _AMP.bf16 and getattr(w, "_hv_amp_bf16", False) else "fp32"
 
 
 _SIDE = {}
@@ -55,38 +97,41 @@ def grad_sink(p):
     return v, acc
 
 
-def mlp_body_forward(x, weights, keep_for_backward):
+def mlp_body_forward(x, weights, keep_for_backward, precisions=None):
     """x W0^T -> SiLU -> ... -> W_last^T  (modules/encoder.py:23-31 of the reference, no biases).
-    Returns y and, for the backward, the per-layer (input, pre-activation) tensors."""
+    Returns y and, for the backward, the per-layer (input, pre-activation) tensors.  precisions: per layer, "fp32" (default) / "bf16"."""
     saved = []
     h = x
     last = len(weights) - 1
     for j, w in enumerate(weights):
+        prec = precisions[j] if precisions is not None else "fp32"
         if j == last:
-            out = _C.gemm(_C.GEMM_NT, h, w)
+            out = _C.gemm(_C.GEMM_NT, h, w, precision=prec)
             saved.append((h, None))
         else:
             pre = torch.empty((h.shape[0], w.shape[0]), device=h.device, dtype=torch.float32) if keep_for_backward else None
-            out = _C.gemm(_C.GEMM_NT, h, w, epilogue=_C.EPI_SILU, aux=pre)
+            out = _C.gemm(_C.GEMM_NT, h, w, epilogue=_C.EPI_SILU, aux=pre, precision=prec)
             saved.append((h, pre))
         h = out
     return h, saved
 
 
-def mlp_body_backward(saved, weights, g_y, need_input_grad, in_pre=None):
+def mlp_body_backward(saved, weights, g_y, need_input_grad, in_pre=None, precisions=None):
     """One launch per layer: dW_j = g_j^T h_{j-1} and g_{j-1} = (g_j W_j) * silu'(pre_{j-1}) share a grid (hidvae_linear_bwd).
-    in_pre: the stack's input was silu(in_pre) and the gradient wanted is the one w.r.t. in_pre (MLPBackFn)."""
+    in_pre: the stack's input was silu(in_pre) and the gradient wanted is the one w.r.t. in_pre (MLPBackFn).
+    precisions: those of the forward (a layer's backward reads its operands at the precision its forward did)."""
     grads = [None] * len(weights)
     g = g_y
     for j in range(len(weights) - 1, -1, -1):
         inp, _ = saved[j]
         dst, acc = grad_sink(weights[j])
+        prec = precisions[j] if precisions is not None else "fp32"
         if j > 0:
-            gw, g = _C.linear_bwd(g, inp, weights[j], True, _C.EPI_DSILU, saved[j - 1][1], dW=dst, accumulate=acc)
+            gw, g = _C.linear_bwd(g, inp, weights[j], True, _C.EPI_DSILU, saved[j - 1][1], dW=dst, accumulate=acc, precision=prec)
         elif in_pre is not None and need_input_grad:
-            gw, g = _C.linear_bwd(g, inp, weights[j], True, _C.EPI_DSILU, in_pre, dW=dst, accumulate=acc)
+            gw, g = _C.linear_bwd(g, inp, weights[j], True, _C.EPI_DSILU, in_pre, dW=dst, accumulate=acc, precision=prec)
         else:
-            gw, g = _C.linear_bwd(g, inp, weights[j], need_input_grad, dW=dst, accumulate=acc)
+            gw, g = _C.linear_bwd(g, inp, weights[j], need_input_grad, dW=dst, accumulate=acc, precision=prec)
         grads[j] = None if dst is not None else gw  # written in place: autograd has nothing to add
     return g, grads, []
 
@@ -95,7 +140,8 @@ class MLPBodyFn(Function):
     @staticmethod
     def forward(ctx, x, *weights):
         ctx.set_materialize_grads(False)
-        y, saved = mlp_body_forward(x, weights, any(ctx.needs_input_grad))
+        ctx.precisions = [precision_of(w) for w in weights]
+        y, saved = mlp_body_forward(x, weights, any(ctx.needs_input_grad), ctx.precisions)
         ctx.saved = saved
         ctx.weights = weights
         ctx.need_x = ctx.needs_input_grad[0]
@@ -105,7 +151,7 @@ class MLPBodyFn(Function):
     def backward(ctx, g_y):
         if g_y is None:
             return (None,) * (1 + len(ctx.weights))
-        gx, gws, keep = mlp_body_backward(ctx.saved, ctx.weights, g_y.contiguous(), ctx.need_x)
+        gx, gws, keep = mlp_body_backward(ctx.saved, ctx.weights, g_y.contiguous(), ctx.need_x, precisions=ctx.precisions)
         for t in keep:
             t.record_stream(side_stream())  # read by the helper stream after this frame is gone
         ctx.saved = None
@@ -122,10 +168,11 @@ class MLPFrontFn(Function):
     @staticmethod
     def forward(ctx, x, *weights):
         ctx.set_materialize_grads(False)
+        ctx.precisions = [precision_of(w) for w in weights]
         saved, h = [], x
-        for w in weights:
+        for w, prec in zip(weights, ctx.precisions):
             pre = torch.empty((h.shape[0], w.shape[0]), device=h.device, dtype=torch.float32)
-            out = _C.gemm(_C.GEMM_NT, h, w, epilogue=_C.EPI_SILU, aux=pre)
+            out = _C.gemm(_C.GEMM_NT, h, w, epilogue=_C.EPI_SILU, aux=pre, precision=prec)
             saved.append((h, pre))
             h = out
         pre_last = saved[-1][1]
@@ -138,7 +185,7 @@ class MLPFrontFn(Function):
     def backward(ctx, g_pre, _g_h):
         if g_pre is None:
             return (None,) * (1 + len(ctx.weights))
-        gx, gws, _ = mlp_body_backward(ctx.saved, ctx.weights, g_pre.contiguous(), ctx.need_x)
+        gx, gws, _ = mlp_body_backward(ctx.saved, ctx.weights, g_pre.contiguous(), ctx.need_x, precisions=ctx.precisions)
         ctx.saved = None
         _C.phase_mark("bwd:encoder front done")
         return (gx,) + tuple(gws)
@@ -150,7 +197,8 @@ class MLPBackFn(Function):
     @staticmethod
     def forward(ctx, pre_in, act_in, *weights):
         ctx.set_materialize_grads(False)
-        y, saved = mlp_body_forward(act_in, weights, any(ctx.needs_input_grad))
+        ctx.precisions = [precision_of(w) for w in weights]
+        y, saved = mlp_body_forward(act_in, weights, any(ctx.needs_input_grad), ctx.precisions)
         ctx.saved, ctx.weights, ctx.pre_in, ctx.need_x = saved, weights, pre_in, ctx.needs_input_grad[0]
         return y
 
@@ -159,7 +207,7 @@ class MLPBackFn(Function):
         if g_y is None:
             return (None,) * (2 + len(ctx.weights))
         _C.phase_mark("bwd:decoder tail start")
-        gx, gws, _ = mlp_body_backward(ctx.saved, ctx.weights, g_y.contiguous(), ctx.need_x, in_pre=ctx.pre_in)
+        gx, gws, _ = mlp_body_backward(ctx.saved, ctx.weights, g_y.contiguous(), ctx.need_x, in_pre=ctx.pre_in, precisions=ctx.precisions)
         _C.phase_mark("bwd:decoder tail done")
         ctx.saved = None
         return (gx, None) + tuple(gws)
@@ -504,6 +552,8 @@ class LinearFn(Function):
         ctx.set_materialize_grads(False)
         need = any(ctx.needs_input_grad)
         pre = None
+        # (a layer whose output a fused fp32 launch produced is an fp32 layer: HRqVae.amp_bf16_parameters never lists one)
+        ctx.precision = precision_of(w) if computed is None else "fp32"
         if computed is not None:
             if act in (_C.EPI_SILU, _C.EPI_GELU) or tuple(computed.shape) != (x.shape[0], w.shape[0]):
                 raise RuntimeError("LinearFn: a precomputed output needs a ReLU / identity layer of the same shape")
@@ -511,7 +561,8 @@ class LinearFn(Function):
         else:
             if need and act in (_C.EPI_SILU, _C.EPI_GELU):
                 pre = torch.empty((x.shape[0], w.shape[0]), device=x.device, dtype=torch.float32)
-            y = _C.gemm(_C.GEMM_NT, x, w, bias=b, epilogue=act, aux=pre, mask=keep_mask, mask_scale=keep_scale, split_k=0)
+            y = _C.gemm(_C.GEMM_NT, x, w, bias=b, epilogue=act, aux=pre, mask=keep_mask, mask_scale=keep_scale, split_k=0,
+                        precision=ctx.precision)
         ctx.act, ctx.keep_scale = act, keep_scale
         ctx.has_bias = b is not None
         ctx.w_param, ctx.b_param = w, b  # (the objects themselves: a flat-gradient slot hangs off the Parameter)
@@ -540,11 +591,12 @@ class LinearFn(Function):
         dst, acc = grad_sink(ctx.w_param)
         if ctx.has_bias:  # weight, input and bias gradients share one launch
             bdst, bacc = grad_sink(ctx.b_param)
-            gw, gx, gb = _C.linear_bwd(g, x, w, ctx.need_x, epi, aux, dW=dst, accumulate=acc, bias=True, db=bdst, accumulate_db=bacc, dx_scale=dxs)
+            gw, gx, gb = _C.linear_bwd(g, x, w, ctx.need_x, epi, aux, dW=dst, accumulate=acc, bias=True, db=bdst, accumulate_db=bacc, dx_scale=dxs,
+                                       precision=ctx.precision)
             if bdst is not None:
                 gb = None
         else:
-            gw, gx = _C.linear_bwd(g, x, w, ctx.need_x, epi, aux, dW=dst, accumulate=acc, dx_scale=dxs)
+            gw, gx = _C.linear_bwd(g, x, w, ctx.need_x, epi, aux, dW=dst, accumulate=acc, dx_scale=dxs, precision=ctx.precision)
             gb = None
         if dst is not None:
             gw = None

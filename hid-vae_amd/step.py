@@ -34,10 +34,14 @@ class GraphedTrainStep:
     row = step(batches)   # batches: list of `ga` batch records (x [, tags_emb, tags_indices]) of the example's shapes
     `row` is a device tensor [6] = (total loss, mean recon, mean rqvae, tag align, tag pred, tag accuracy) that the NEXT call
     overwrites: clone it to keep it.  The first calls run eagerly (allocator / kernel-attribute warm-up, and the randomness
-    provider learns the step's dropout requests); the capture happens on call number `warmup + 1`."""
+    provider learns the step's dropout requests); the capture happens on call number `warmup + 1`.
+    autocast_dtype=torch.bfloat16: every forward of the step (the eager warm-up calls and the captured one) runs under
+    torch.autocast("cuda", dtype=torch.bfloat16) -- the amp mode, a host-side choice baked into the graph; the backward
+    runs outside it, as the reference's accelerator.autocast() block leaves it."""
 
-    def __init__(self, model, opt, example_batches, dp=None, gumbel_t=0.2, warmup=3, enabled=True, overlap=None):
+    def __init__(self, model, opt, example_batches, dp=None, gumbel_t=0.2, warmup=3, enabled=True, overlap=None, autocast_dtype=None):
         self.model, self.opt, self.dp, self.t = model, opt, dp, gumbel_t
+        self.autocast_dtype = autocast_dtype
         self.ga = len(example_batches)
         self.tagged = getattr(example_batches[0], "tags_emb", None) is not None
         self.static = []
@@ -75,12 +79,14 @@ class GraphedTrainStep:
 
     @contextlib.contextmanager
     def _armed(self):
-        """the model knows the loss gradient / the per-level optimizer hook only inside this block"""
+        """the model knows the loss gradient / the per-level optimizer hook only inside this block (and runs under the step's autocast)"""
         m = self.model
         saved = (getattr(m, "loss_grad_hint", None), getattr(m, "_level_done_hook", None))
         m.loss_grad_hint, m._level_done_hook = self.loss_grad_hint, self.level_done_hook
+        amp = torch.autocast("cuda", dtype=self.autocast_dtype) if self.autocast_dtype is not None else contextlib.nullcontext()
         try:
-            yield
+            with amp:
+                yield
         finally:
             m.loss_grad_hint, m._level_done_hook = saved
 

@@ -92,6 +92,20 @@ def _load_items(dataset, dataset_folder, device, n_layers, class_counts, tag_emb
     return full.subset(is_train), full.subset(~is_train), full
 
 
+def amp_dtype(amp, mixed_precision_type):
+    """(amp, mixed_precision_type) of train() -> the autocast dtype of the training step, None for fp32: what the reference's
+    Accelerator(mixed_precision=mixed_precision_type if amp else 'no') sets up (train_hidvae.py:186-189).  Only bf16 is built (the amp
+    mode); fp16 would need dynamic loss scaling, which the early per-level AdamW of the step cannot take."""
+    if not amp or mixed_precision_type == "no":
+        return None
+    if mixed_precision_type == "bf16":
+        return torch.bfloat16
+    if mixed_precision_type in ("fp16", "fp8"):
+        raise NotImplementedError(f"amp with mixed_precision_type={mixed_precision_type!r}: the HIP path implements \"bf16\" only "
+                                  "(bf16 operands on the Linear layers, fp32 elsewhere)")
+    raise ValueError(f"mixed_precision_type={mixed_precision_type!r}: expected 'no', 'fp16', 'bf16' or 'fp8'")
+
+
 @gin.configurable
 def train(iterations=50000, batch_size=64, learning_rate=0.0001, weight_decay=0.01, dataset_folder="dataset/ml-1m", dataset=None,
           pretrained_hrqvae_path=None, save_dir_root="out/", use_kmeans_init=True, split_batches=True, amp=False, do_eval=True,
@@ -107,8 +121,7 @@ def train(iterations=50000, batch_size=64, learning_rate=0.0001, weight_decay=0.
           lr_scheduler_factor=0.5, lr_scheduler_patience=10, sem_id_uniqueness_weight=0.5, sem_id_uniqueness_margin=0.5,
           id_repetition_threshold=0.03, use_concatenated_ids=False, use_interleaved_ids=False, seed=0, log_every=100,
           use_hip_graph=True):
-    if amp:
-        raise NotImplementedError("amp is False in every reference config; the HIP path computes in fp32")
+    autocast_dtype = amp_dtype(amp, mixed_precision_type)  # (the k-means warm-up, evaluate() and the tokenizer run without it)
     if lr_scheduler_type not in ("cosine", "step"):
         raise ValueError(f"unsupported lr_scheduler_type {lr_scheduler_type}")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -235,7 +248,7 @@ def train(iterations=50000, batch_size=64, learning_rate=0.0001, weight_decay=0.
         # (once the step object exists the batches are gathered straight into its input buffers: no per-step copy)
         micro = [sampler.next(out=stepper.input_buffers(j) if stepper is not None else None) for j in range(ga)]
         if stepper is None:  # built on the first regular step: its static buffers take the batch shapes
-            stepper = GraphedTrainStep(model, opt, micro, dp=dp, gumbel_t=t, enabled=use_hip_graph)
+            stepper = GraphedTrainStep(model, opt, micro, dp=dp, gumbel_t=t, enabled=use_hip_graph, autocast_dtype=autocast_dtype)
         row = stepper(micro)  # device [6]: total loss, mean recon, mean rqvae, tag align, tag pred, tag accuracy
         window.append(row.clone())
         if it % log_every == 0 and main_proc:

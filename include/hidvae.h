@@ -82,6 +82,11 @@ const char *hidvae_last_error(void);
 #define HIDVAE_WS_LINEAR_BWD_ZEROED 12   /* B, n_out, n_in, has_bias  -> leading bytes of the hidvae_linear_bwd workspace that must be ZERO
                                             on entry (arrival counters of the balanced kernel; left zero on return).  Non-zero means: hand
                                             hidvae_linear_bwd a workspace that no launch running CONCURRENTLY shares (one per stream). */
+#define HIDVAE_WS_LINEAR_BWD_BF16 14     /* B, n_out, n_in, has_bias  -> hidvae_linear_bwd_bf16 workspace (every shape)                 */
+#define HIDVAE_WS_GEMM_BF16 15           /* M, N, K                   -> hidvae_gemm_bf16 workspace (every shape)                        */
+#define HIDVAE_WS_BF16_ZEROED 16         /* (no dimensions needed)    -> leading bytes of either bf16 workspace that must be ZERO on entry
+                                            (arrival counters; left zero on return): the contract of HIDVAE_WS_LINEAR_BWD_ZEROED, at every
+                                            shape.  One buffer per stream serves the fp32 and the bf16 entries alike. */
 int hidvae_query_workspace(int op, const int64_t *dims, int n_dims, int64_t *bytes);
 
 /* ---- a2/a3/a9/a10: Linear layers (modules/encoder.py:23-36, h_rqvae.py:132-188,322-331) ------------
@@ -151,6 +156,39 @@ typedef struct {
     float *workspace;
 } hidvae_linear_bwd_problem;
 int hidvae_linear_bwd_group(const hidvae_linear_bwd_problem *problems_host, int n, void *stream);
+
+/* ---- bf16-operand forms of the Linear layers (the amp mode: DESIGN.md 4.5).  fp32 in HBM, fp32 out, fp32 epilogues; every operand
+ * element is rounded to bf16 (round to nearest even, as torch's .bfloat16()) where the kernel reads it, products accumulate in fp32 on
+ * v_mfma_f32_32x32x16_bf16.  Products of bf16 values are exact in fp32, so a result differs from the float64 product of the ROUNDED
+ * operands only by the fp32 accumulation.  Each runs on the LDS-DMA ring (64x64 tiles whose k-steps are dealt evenly over the chip,
+ * partial tiles added in ascending k order by the last workgroup to arrive): deterministic, bit-identical from launch to launch, at
+ * every shape.  `workspace` is required: hidvae_query_workspace(HIDVAE_WS_GEMM_BF16 / HIDVAE_WS_LINEAR_BWD_BF16) bytes whose leading
+ * HIDVAE_WS_BF16_ZEROED bytes are zero on entry and are zero again on return, never shared with a launch that may run at the same
+ * time (one buffer per stream).  Operands of more than 2^29 elements are refused.
+ *
+ * y = x W^T as hidvae_gemm_f32(HIDVAE_GEMM_NT, ...) computes it: C[M,N] (ldc) = epilogue(A[M,K] B[N,K]^T + bias[N]) [* dropout];
+ * forward epilogues only (NONE, SILU / GELU with the pre-activation into aux when given, RELU, SIGMOID); dropout by keep-mask * mask_scale
+ * or decided in the launch from rng_state / rng_site / drop_threshold with the element index row * N + col of hidvae_gemm_f32, so the keep
+ * pattern is that kernel's; accumulate != 0 adds into C.  No layout (NT only) and no split_k (the ring picks its split). */
+int hidvae_gemm_bf16(int64_t M, int64_t N, int64_t K,
+                     const float *A, int64_t lda, const float *B, int64_t ldb,
+                     const float *bias, float *C, int64_t ldc,
+                     int epilogue, float *aux, int64_t ldaux,
+                     const float *mask, int64_t ldmask, float mask_scale,
+                     const unsigned long long *rng_state, unsigned rng_site, unsigned drop_threshold,
+                     float *workspace, int accumulate, void *stream);
+
+/* hidvae_linear_bwd with bf16 operands: dW [n_out, n_in] (+)= g^T x, dX [B, n_in] = epi(g W) (D* epilogue with aux, dx_scale on DRELU;
+ * dX == NULL: weight gradient only), db [n_out] (+)= column sums of g in fp32 (db == NULL: none), in one launch (dX in row chunks
+ * beyond ~20000 rows at 768 wide).  g, x and W are rounded to bf16 where they are read; no co_resident (one workgroup shape). */
+int hidvae_linear_bwd_bf16(const float *g, int64_t ldg, const float *x, int64_t ldx, const float *W, int64_t ldw, int64_t B,
+                           int64_t n_out, int64_t n_in, float *dW, int64_t lddw, int accumulate_dw, float *dX, int64_t lddx,
+                           int dx_epilogue, float *aux, int64_t ldaux, float dx_scale, float *db, int accumulate_db, float *workspace,
+                           void *stream);
+
+/* hidvae_linear_bwd_bf16 of each problem in order (one launch each; dx_scale 1), so every result is bit-identical to the single call.
+ * Each problem's `workspace` follows the contract above; launches of one call are serialised, so one buffer may serve them all. */
+int hidvae_linear_bwd_group_bf16(const hidvae_linear_bwd_problem *problems_host, int n, void *stream);
 
 /* out[n] (+)= sum_m X[m,n]   (bias gradients; fixed summation order, bit-reproducible).  One launch for M <= 16384 (no
  * workspace needed, may be NULL); above that two fixed-order passes through workspace >= ceil(M/64)*N floats. */

@@ -41,7 +41,8 @@ __device__ __forceinline__ float hv_expE(float x) {
     float y = fmaf(p, r * r, r) + 1.0f;
     return ldexpf(y, (int)n);
 }
-__device__ __forceinline__ float hv_sigmoid(float a) { return 1.0f / (1.0f + hv_expE(-a)); }
+// (a NaN stays NaN, as in torch: hv_expE's clamp would turn it into a finite value and the sigmoid into 0 or 1)
+__device__ __forceinline__ float hv_sigmoid(float a) { return __builtin_isnan(a) ? a : 1.0f / (1.0f + hv_expE(-a)); }
 __device__ __forceinline__ float hv_silu(float a) { return a / (1.0f + hv_expE(-a)); }
 __device__ __forceinline__ float hv_dsilu(float a) {
     float s = hv_sigmoid(a);
@@ -60,7 +61,7 @@ __device__ __forceinline__ float hv_dgelu(float a) {
 __device__ __forceinline__ float hv_apply_epilogue(int epi, float v, const float *aux, int64_t off, float scale = 1.0f) {
     switch (epi) {
         case HIDVAE_EPI_SILU: return hv_silu(v);
-        case HIDVAE_EPI_RELU: return fmaxf(v, 0.0f);
+        case HIDVAE_EPI_RELU: return __builtin_isnan(v) ? v : fmaxf(v, 0.0f);  // (fmaxf alone drops a NaN; torch's relu keeps it)
         case HIDVAE_EPI_GELU: return hv_gelu(v);
         case HIDVAE_EPI_SIGMOID: return hv_sigmoid(v);
         case HIDVAE_EPI_DSILU: return v * hv_dsilu(aux[off]);

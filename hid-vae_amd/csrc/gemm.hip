@@ -1835,7 +1835,10 @@ static int linear_bwd_impl(const float *g, int64_t ldg, const float *x, int64_t 
         // the LDS-DMA ring kernel (gemm_ring.hip) wherever it takes the problem; the kernels below are what runs when it declines.
         // (First shipped from B = 2048 on, where it won stand-alone; in the step it also wins at B = 1024: tagged 1.156 -> 1.088 ms
         // together with the lower threshold of rules.h -- profiles/r04_ring_threshold_ab.log.)
-        {
+        // Not for dX from a view of g whose rows are not a multiple of 16 bytes: the ring kernel reads g's rows in 16-byte pieces and
+        // leaves the piece that straddles n_out to W's zeroed rows past n_out to cancel -- the next row's values in a contiguous g, but a
+        // view's padding may hold NaN or Inf, and 0 * NaN is NaN.  gemm_mid_sk_kernel zeroes that piece where it reads it.
+        if (dX == nullptr || ldg == n_out || n_out % 4 == 0) {
             const int rc = hv_ring_linear_bwd(g, ldg, x, ldx, W, ldw, B, n_out, n_in, dW, lddw, accumulate_dw, dX, lddx, dx_epilogue, aux, ldaux,
                                               dx_scale, db, accumulate_db, workspace, 512, (hipStream_t)stream);
             if (rc != 1) return rc;

@@ -376,9 +376,11 @@ def test_linear_bwd_balanced_kernel_against_float64_and_itself(C, B, n_out, n_in
 
 @pytest.mark.parametrize("B,n_out,n_in", [(1024, 768, 512), (1024, 691, 768), (1000, 460, 512), (1024, 345, 691), (2048, 512, 256)])
 def test_linear_bwd_on_an_announced_side_stream_takes_the_small_workgroups(C, B, n_out, n_in):
-    """co_resident: on a stream announced with register_ws_lane the balanced kernel runs eight-wave workgroups (two per CU) where it
-    can take whole tiles -- same contract: float64 parity incl. the gated epilogue, accumulate, db; launch-to-launch bit identity;
-    clean counters; within rounding of the sixteen-wave form"""
+    """co_resident: a Linear backward issued on a stream announced with register_ws_lane -- same contract as on the caller's stream:
+    float64 parity incl. the gated epilogue, accumulate, db; launch-to-launch bit identity; clean counters; within rounding of the
+    caller's-stream result.  These contiguous shapes all run on the ring kernel (gemm_ring_bwd_kernel), which takes every shape
+    hv_lbwd_balanced admits; co_resident selects the eight-wave gemm_mid_sk_kernel<2,2> only where the ring kernel is declined (dX
+    from a view of g whose rows are not a multiple of 16 bytes: test_linear_bwd_paths_gpu covers it)"""
     g, x, w = dev(fill.gauss((B, n_out), 84)), dev(fill.gauss((B, n_in), 85)), dev(fill.gauss((n_out, n_in), 86))
     y = dev(np.maximum(fill.gauss((B, n_in), 87), 0.0))
     gd, xd, wd = g.cpu().double(), x.cpu().double(), w.cpu().double()

@@ -94,6 +94,9 @@ _SIGNATURES = {
     "hidvae_gemm_bf16": [_i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i, _vp, _i64, _vp, _i64, _f, _vp, _u32, _u32, _vp, _i, _vp],
     "hidvae_linear_bwd_bf16": [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i, _vp, _i64, _i, _vp, _i64, _f, _vp, _i, _vp, _vp],
     "hidvae_linear_bwd_group_bf16": [_vp, _i, _vp],
+    "hidvae_prefix_pack": [_vp, _i64, _i64, _i, _vp, _vp, _vp, _vp],
+    "hidvae_prefix_exists": [_vp, _i, _i64, _i64, _i, _vp, _vp, _i, _vp, _i64, _i64, _vp, _vp],
+    "hidvae_prefix_next": [_vp, _i, _i64, _i64, _i, _vp, _vp, _i, _vp, _i64, _i64, _vp, _vp],
 }
 WS_GEMM, WS_LINEAR_BWD, WS_COLSUM, WS_CODEBOOK_GRAD, WS_LAYERNORM_PARAM_GRAD, WS_LAYERNORM_BWD_ALL = 1, 2, 3, 4, 5, 6
 WS_BATCHNORM_FWD, WS_BATCHNORM_BWD, WS_ID_CENSUS, WS_KMEANS, WS_TAG_LOSS, WS_LINEAR_BWD_ZEROED, WS_RQ_FORWARD = 7, 8, 9, 10, 11, 12, 13
@@ -1421,3 +1424,58 @@ def gather_rows(idx, tables, outs):
     _check(lib().hidvae_gather_rows(_p(idx), rows, n, vp(*[t.data_ptr() for t in tables]), vp(*[o.data_ptr() for o in outs]), i64(*rb), i64(*sr),
                                     _stream()), "hidvae_gather_rows")
     return outs
+
+
+# ------------------------------------------------------------------------------------------------ prefix index (constrained decoding)
+PREFIX_MAX_W = 64
+PREFIX_KEY_LIMIT = 1 << 62
+
+
+class PrefixPlan:
+    """the mixed-radix plan of an index's first W columns as the host arrays the prefix entry points take (built once per index)"""
+    __slots__ = ("W", "lo", "radix")
+
+    def __init__(self, lo, radix):
+        if not 1 <= len(lo) == len(radix) <= PREFIX_MAX_W:
+            raise RuntimeError(f"prefix plan of {len(lo)} / {len(radix)} columns (1 .. {PREFIX_MAX_W}, equally many)")
+        self.W = len(lo)
+        self.lo = (ctypes.c_int64 * self.W)(*[int(v) for v in lo])
+        self.radix = (ctypes.c_int64 * self.W)(*[int(v) for v in radix])
+
+
+def _query_rows(q, name):
+    """(pointer, entry bytes, row stride) of int32 / int64 device rows [n, >= w] with a contiguous last dim"""
+    if not q.is_cuda or q.dim() != 2 or q.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError(f"{name}: expected int32 / int64 device rows [n, w], got {q.dtype} {tuple(q.shape)} on {q.device}")
+    return _p(q), q.element_size(), _row_stride(q, name)
+
+
+def prefix_pack(ids, plan):
+    """ids [N, >= plan.W] int64 device rows -> keys [N] int64: the mixed-radix key of every row's first plan.W columns, -1 for a row
+    with an entry outside the plan (hidvae_prefix_pack)"""
+    if ids.dtype != torch.int64 or not ids.is_cuda or ids.dim() != 2 or ids.shape[1] < plan.W:
+        raise RuntimeError(f"prefix_pack: expected int64 device rows [N, >= {plan.W}], got {ids.dtype} {tuple(ids.shape)}")
+    keys = torch.empty((ids.shape[0],), device=ids.device, dtype=torch.int64)
+    _check(lib().hidvae_prefix_pack(_p(ids), ids.shape[0], _row_stride(ids, "ids"), plan.W, plan.lo, plan.radix, _p(keys), _stream()),
+           "hidvae_prefix_pack")
+    return keys
+
+
+def prefix_exists(q, w, plan, keys, n_covered):
+    """q [n, >= w] int32 / int64 device rows -> bool [n]: are the row's first w entries the first w columns of an indexed row (keys:
+    the sorted unique keys of prefix_pack); rows from n_covered on are False (hidvae_prefix_exists, one launch)"""
+    qp, qb, ldq = _query_rows(q, "prefix_exists")
+    out = torch.empty((q.shape[0],), device=q.device, dtype=torch.bool)
+    _check(lib().hidvae_prefix_exists(qp, qb, q.shape[0], ldq, int(w), plan.lo, plan.radix, plan.W, _p(keys), keys.numel(),
+                                      int(n_covered), _p(out), _stream()), "hidvae_prefix_exists")
+    return out
+
+
+def prefix_next(q, n, w, plan, keys, V, device):
+    """q [n, >= w] int32 / int64 device rows (None when w = 0) -> bool [n, V]: may id v follow the row's first w entries in some
+    indexed row (hidvae_prefix_next, one launch)"""
+    qp, qb, ldq = _query_rows(q, "prefix_next") if w > 0 else (None, 8, 0)
+    out = torch.empty((n, V), device=device, dtype=torch.bool)
+    _check(lib().hidvae_prefix_next(qp, qb, int(n), ldq, int(w), plan.lo, plan.radix, plan.W, _p(keys), keys.numel(), int(V), _p(out),
+                                    _stream()), "hidvae_prefix_next")
+    return out

@@ -1,10 +1,11 @@
 """HSemanticIdTokenizer on the HIP path (reference modules/tokenizer/h_semids.py:24-532): owns an eval-mode HRqVae,
 turns item features into semantic-id tuples (optionally concatenated / interleaved with predicted tag ids), caches the
-corpus ids and answers prefix-existence queries for constrained decoding.
+corpus ids and answers prefix queries for constrained decoding: does a prefix exist (`exists_prefix`), and which ids may follow it
+(`valid_next_ids`, not in the reference).
 
 Differences in HOW (not what): the corpus is encoded in large resident chunks through the fused encode + RQ kernels
-instead of 512-item DataLoader batches, and `exists_prefix` is a sorted-key binary search (one sort per prefix length,
-cached) instead of a [queries, corpus, L] broadcast compare."""
+instead of 512-item DataLoader batches, and the prefix queries are binary searches in one sorted-key index per cache (built on
+first use, prefix_index.py; one launch per call) instead of a [queries, corpus, L] broadcast compare."""
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -12,8 +13,8 @@ from torch import Tensor, nn
 
 from ...data.schemas import SeqBatch, TokenizedSeqBatch
 from ..h_rqvae import HRqVae
+from .prefix_index import BATCH_SIZE, PrefixIndex, position_vocab  # noqa: F401  (BATCH_SIZE: the reference's module constant)
 
-BATCH_SIZE = 16  # the reference checks prefixes in groups of 16 (h_semids.py:22,218)
 CORPUS_CHUNK = 65536
 
 
@@ -60,9 +61,9 @@ class HSemanticIdTokenizer(nn.Module):
 
     @cached_ids.setter
     def cached_ids(self, ids):
-        # (an assignment from outside drops the sorted-prefix index and the knowledge that every id is below the codebook size)
+        # (an assignment from outside drops the prefix index and the knowledge that every id lies in its position's vocabulary)
         self.__dict__["_cached_ids"] = ids
-        self._prefix_index = {}
+        self._prefix_index = None
         self._ids_trusted = False
 
     @property
@@ -123,47 +124,59 @@ class HSemanticIdTokenizer(nn.Module):
         else:
             parts = [self._ids_for(feats[i:i + CORPUS_CHUNK]) for i in range(0, feats.shape[0], CORPUS_CHUNK)]
             self.cached_ids = torch.cat(parts, dim=0) if len(parts) > 1 else parts[0]
-        self._prefix_index = {}
+        self._prefix_index = None
         self._ids_trusted = True
         return self.cached_ids
 
     # ------------------------------------------------------------------------------------------------
-    def _keys(self, ids: Tensor, width: int, radix: int) -> Tensor:
-        key = torch.zeros(ids.shape[:-1], dtype=torch.int64, device=ids.device)
-        for j in range(width):
-            key = key * radix + ids[..., j].to(torch.int64)
-        return key
+    def position_vocab(self) -> List[int]:
+        """the number of ids each position of a corpus row can take, in _ids_for's order (tags: the classes of the model's heads)"""
+        tags = self.hrq_vae.tag_class_counts if (self.use_concatenated_ids or self.use_interleaved_ids) else None
+        return position_vocab(self.codebook_size, self.n_layers, tags, self.use_dedup_dim, self.use_concatenated_ids,
+                              self.use_interleaved_ids)
+
+    def _index(self) -> PrefixIndex:
+        # built once per cache: a cache precompute_corpus_ids made is packed over the vocabulary (nothing read back); one assigned from
+        # outside is read once for its column ranges
+        if self._prefix_index is None:
+            self._prefix_index = PrefixIndex(self.cached_ids, self.position_vocab(), getattr(self, "_ids_trusted", False))
+        return self._prefix_index
+
+    def _settle_mode(self):
+        # what the reference's eval_mode wrapper leaves behind -- every submodule in the tokenizer's own mode -- without its two
+        # recursive train() passes (0.4 ms of host time per call): the prefix queries never run the model
+        was = self.training
+        for m in self.modules():
+            if m.training != was:
+                m.training = was
 
     @torch.no_grad()
-    @_eval_mode
     def exists_prefix(self, sem_id_prefix: Tensor) -> Tensor:
+        self._settle_mode()
         if self.cached_ids is None:
             raise Exception("No match found in empty cache.")
         width = min(sem_id_prefix.shape[-1], self.cached_ids.shape[-1])
-        out = torch.zeros(*sem_id_prefix.shape[:-1], dtype=torch.bool, device=sem_id_prefix.device)
         if self.cached_ids.shape[0] == 0 or width == 0:
-            return out
-        if width not in self._prefix_index:
-            # ids produced by precompute_corpus_ids are < codebook_size (semantic) / < the level's class count (predicted tags): the
-            # radix is known without reading the device; a cache assigned from outside is checked once (one host read)
-            bound = max(self.codebook_size - 1, *(self.tag_class_counts or [0]))
-            if not getattr(self, "_ids_trusted", False):
-                bound = max(bound, int(self.cached_ids.max()))
-            radix = int(bound) + 2
-            if radix ** width >= 2 ** 62:
-                raise OverflowError("id prefix does not fit a 64-bit key")
-            self._prefix_index[width] = (radix, torch.sort(self._keys(self.cached_ids[:, :width], width, radix)).values)
-        radix, sorted_keys = self._prefix_index[width]
-        q = sem_id_prefix[..., :width].to(self.cached_ids.device)
-        ok = (q >= 0).all(dim=-1) & (q < radix).all(dim=-1)
-        qk = self._keys(q.clamp(min=0, max=radix - 1), width, radix)
-        pos = torch.searchsorted(sorted_keys, qk).clamp(max=sorted_keys.numel() - 1)
-        hit = ((sorted_keys[pos] == qk) & ok).to(out.device)
-        # the reference walks the rows in floor(rows/16) groups of 16 (h_semids.py:218: math.ceil(B // BATCH_SIZE)), so the
-        # trailing rows % 16 rows are never examined and stay False -- reproduced
-        covered = (sem_id_prefix.shape[0] // BATCH_SIZE) * BATCH_SIZE
-        out[:covered] = hit[:covered]
-        return out
+            return torch.zeros(*sem_id_prefix.shape[:-1], dtype=torch.bool, device=sem_id_prefix.device)
+        if sem_id_prefix.dim() < 2:
+            raise IndexError(f"exists_prefix: expected prefixes [rows, ..., width], got shape {tuple(sem_id_prefix.shape)}")
+        # (the reference walks the rows in floor(rows/16) groups of 16, h_semids.py:218: math.ceil(B // BATCH_SIZE), so the trailing
+        #  rows % 16 rows are never examined and stay False -- reproduced inside the launch)
+        return self._index().exists(sem_id_prefix, width)
+
+    @torch.no_grad()
+    def valid_next_ids(self, sem_id_prefix: Tensor) -> Tensor:
+        """sem_id_prefix [..., w] (0 <= w < cache width) -> bool [..., V'] on the prefix's device, V' = the largest id position w can
+        hold + 1 (its vocabulary for a cache precompute_corpus_ids made): entry v is True iff the prefix (entries >= 0) followed by v
+        equals the first w + 1 ids of some cached item.  The mask a constrained decoder applies before sampling the next id (the
+        reference instead penalises sampled candidates that exists_prefix rejects, modules/model.py:200-219).  Every row is answered:
+        no rows % 16 quirk."""
+        if self.cached_ids is None:
+            raise Exception("No match found in empty cache.")
+        w, W = sem_id_prefix.shape[-1], self.cached_ids.shape[-1]
+        if not 0 <= w < W:
+            raise ValueError(f"valid_next_ids: prefix width {w}, the cache holds {W} ids per item (the next id needs width < {W})")
+        return self._index().next_ids(sem_id_prefix)
 
     # ------------------------------------------------------------------------------------------------
     def _tokenize_seq_batch_from_cached(self, ids: Tensor) -> Tensor:

@@ -598,6 +598,29 @@ int hidvae_jagged_to_padded(const void *values, const int64_t *offsets, void *x,
 int hidvae_gather_rows(const int64_t *idx, int64_t rows, int n_tables, const void *const *src, void *const *dst,
                        const int64_t *row_bytes, const int64_t *src_rows, void *stream);
 
+/* ---- constrained decoding: one prefix index per corpus id cache (csrc/prefix.hip).  A cache row's first W columns are one
+ * mixed-radix key: column j contributes the digit id - lo_host[j] in [0, radix_host[j]) (lo_host[j] <= 0; the radix product of the W
+ * columns below HIDVAE_PREFIX_KEY_LIMIT, W <= HIDVAE_PREFIX_MAX_W), the first column most significant.  The caller sorts and deduplicates the packed keys once
+ * (keys[0 .. n_keys), ascending); then every query is one launch.  Query rows: n_q rows of int32 (q_bytes 4) or int64 (8) entries,
+ * row stride ldq, the first w entries read.  An entry that is negative or outside its column's [lo, lo + radix) matches nothing. */
+#define HIDVAE_PREFIX_MAX_W 64  /* (with every radix >= 2 the 2^62 limit allows at most 61 columns) */
+#define HIDVAE_PREFIX_KEY_LIMIT (INT64_C(1) << 62)
+/* h_semids.py:109-197 (the cache precompute_corpus_ids fills): keys[r] = key of ids row r (row stride ld), or -1 where an entry lies
+ * outside the plan (such a row can match no query). */
+int hidvae_prefix_pack(const int64_t *ids, int64_t n, int64_t ld, int W, const int64_t *lo_host, const int64_t *radix_host,
+                       int64_t *keys, void *stream);
+/* h_semids.py:199-239 exists_prefix: out[r] (torch.bool bytes) = 1 iff some key lies in [key(row r) * S_w, (key(row r) + 1) * S_w),
+ * S_w = prod_{w <= i < W} radix_host[i], i.e. the row's first w entries are the first w columns of some cache row; 1 <= w <= W.  Rows
+ * r >= n_covered are written 0 unread (the reference examines floor(rows / 16) * 16 leading rows only, h_semids.py:218).  Every
+ * element of out[n_q] is written. */
+int hidvae_prefix_exists(const void *q, int q_bytes, int64_t n_q, int64_t ldq, int w, const int64_t *lo_host, const int64_t *radix_host,
+                         int W, const int64_t *keys, int64_t n_keys, int64_t n_covered, uint8_t *out, void *stream);
+/* model.py:200-219 (the decoder samples next ids and penalises the invalid ones): the valid next ids of each prefix.
+ * out[r, v] (torch.bool bytes, row stride V) = 1 iff the row's first w entries followed by v are the first w + 1 columns of some cache
+ * row; 0 <= w < W.  Every element of out[n_q, V] is written; v outside column w's [lo, lo + radix) is 0. */
+int hidvae_prefix_next(const void *q, int q_bytes, int64_t n_q, int64_t ldq, int w, const int64_t *lo_host, const int64_t *radix_host,
+                       int W, const int64_t *keys, int64_t n_keys, int64_t V, uint8_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,8 @@ _SIGNATURES = {
     "hidvae_prefix_pack": [_vp, _i64, _i64, _i, _vp, _vp, _vp, _vp],
     "hidvae_prefix_exists": [_vp, _i, _i64, _i64, _i, _vp, _vp, _i, _vp, _i64, _i64, _vp, _vp],
     "hidvae_prefix_next": [_vp, _i, _i64, _i64, _i, _vp, _vp, _i, _vp, _i64, _i64, _vp, _vp],
+    "hidvae_beam_step": [_vp, _i64, _i64, _i64, _i64, _vp, _i, _i64, _i64, _vp, _i64, _vp, _i, _i, _f, _vp, _vp, _i, _vp, _i64, _vp, _vp, _vp,
+                         _vp, _vp],
 }
 WS_GEMM, WS_LINEAR_BWD, WS_COLSUM, WS_CODEBOOK_GRAD, WS_LAYERNORM_PARAM_GRAD, WS_LAYERNORM_BWD_ALL = 1, 2, 3, 4, 5, 6
 WS_BATCHNORM_FWD, WS_BATCHNORM_BWD, WS_ID_CENSUS, WS_KMEANS, WS_TAG_LOSS, WS_LINEAR_BWD_ZEROED, WS_RQ_FORWARD = 7, 8, 9, 10, 11, 12, 13
@@ -1479,3 +1481,40 @@ def prefix_next(q, n, w, plan, keys, V, device):
     _check(lib().hidvae_prefix_next(qp, qb, int(n), ldq, int(w), plan.lo, plan.radix, plan.W, _p(keys), keys.numel(), int(V), _p(out),
                                     _stream()), "hidvae_prefix_next")
     return out
+
+
+BEAM_MAX_K = 64
+BEAM_MAX_CANDIDATES = 32768
+
+
+def beam_step(logits, candidates, generated, log_probas, B, k, temperature, plan, keys):
+    """one constrained beam-search step (hidvae_beam_step, one launch): logits [B * k_prev, V] fp32, candidates [B * k_prev, C] int32 /
+    int64 or None (every id in order), generated [B * k_prev, w] int64 or None (w = 0), log_probas [B * k_prev] fp32 or None ->
+    (sem_ids [B, k, w + 1] int64, log_probas [B, k] fp32, parents [B, k] int64, valid [B, k] bool)"""
+    _f32(logits, "beam_step")
+    ldl = _row_stride(logits, "beam_step")
+    rows, V = logits.shape
+    k_prev = rows // B if B else 1
+    cp, cb, ldc, C = None, 0, 0, V
+    if candidates is not None:
+        cp, cb, ldc = _query_rows(candidates, "beam_step")
+        C = candidates.shape[1]
+    gp, ldg, w = None, 0, 0
+    if generated is not None:
+        if generated.dtype != torch.int64:
+            raise RuntimeError(f"beam_step: expected int64 generated ids, got {generated.dtype}")
+        gp, _, ldg = _query_rows(generated, "beam_step")
+        w = generated.shape[1]
+    if log_probas is not None:
+        _f32(log_probas, "beam_step")
+        if log_probas.dim() != 1 or (log_probas.numel() > 1 and log_probas.stride(0) != 1):
+            raise RuntimeError("beam_step: expected contiguous log_probas [B * k_prev]")
+    dev = logits.device
+    ids = torch.empty((B, k, w + 1), device=dev, dtype=torch.int64)
+    logp = torch.empty((B, k), device=dev, dtype=torch.float32)
+    parents = torch.empty((B, k), device=dev, dtype=torch.int64)
+    valid = torch.empty((B, k), device=dev, dtype=torch.bool)
+    _check(lib().hidvae_beam_step(_p(logits), ldl, int(B), int(k_prev), int(V), cp, cb, ldc, int(C), gp, ldg, _p(log_probas), int(w), int(k),
+                                  float(temperature), plan.lo, plan.radix, plan.W, _p(keys), keys.numel(), _p(ids), _p(logp), _p(parents),
+                                  _p(valid), _stream()), "hidvae_beam_step")
+    return ids, logp, parents, valid

@@ -3,42 +3,11 @@
 // (column j: digit id - lo[j] in [0, radix[j]), first column most significant); the keys are sorted and deduplicated once per cache
 // (plumbing, outside the decode loop).  A prefix p of width w then owns the key range [key(p) * S_w, (key(p) + 1) * S_w) with
 // S_w = prod_{i >= w} radix[i]: it exists iff a key lies in that range (one lower_bound), and digit d may follow it iff a key lies in
-// [(key(p) * radix[w] + d) * S_{w+1}, ... + S_{w+1}).  So one index answers every width, and every call is one launch.
-#include "common.h"
+// [(key(p) * radix[w] + d) * S_{w+1}, ... + S_{w+1}).  So one index answers every width, and every call is one launch.  The plan and the
+// search helpers live in prefix.h (beam.hip reads the same index).
+#include "prefix.h"
 
 namespace {
-
-struct PrefixPlan {
-    int64_t lo[HIDVAE_PREFIX_MAX_W];
-    int64_t radix[HIDVAE_PREFIX_MAX_W];
-};
-
-// key of the first w columns of `row`; false when an entry lies outside its column's [lo, lo + radix) (QUERY: or is negative)
-template <bool QUERY, typename T>
-__device__ __forceinline__ bool pack_row(const T *row, int w, const PrefixPlan &p, int64_t &key) {
-    int64_t k = 0;
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < HIDVAE_PREFIX_MAX_W; j++) {
-        if (j >= w) break;  // (w is uniform: the unrolled loop keeps the plan in scalar registers)
-        const int64_t v = (int64_t)row[j];
-        const int64_t d = v - p.lo[j];
-        ok = ok && d >= 0 && d < p.radix[j] && (!QUERY || v >= 0);
-        k = k * p.radix[j] + (ok ? d : 0);
-    }
-    key = k;
-    return ok;
-}
-
-// first index in [a, b) whose key is >= x (b when none)
-__device__ __forceinline__ int64_t lower_bound(const int64_t *keys, int64_t a, int64_t b, int64_t x) {
-    while (a < b) {
-        const int64_t mid = a + ((b - a) >> 1);
-        if (keys[mid] < x) a = mid + 1;
-        else b = mid;
-    }
-    return a;
-}
 
 __global__ __launch_bounds__(256) void prefix_pack_kernel(const int64_t *ids, int64_t n, int64_t ld, int W, PrefixPlan p, int64_t *keys) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -94,24 +63,6 @@ __global__ __launch_bounds__(256) void prefix_next_kernel(const T *q, int64_t n_
         }
         o[v] = hit;
     }
-}
-
-// validates the host plan of the first W columns; spans[w] = prod_{w <= i < W} radix[i] (< 2^62 by construction)
-int read_plan(const int64_t *lo_host, const int64_t *radix_host, int W, PrefixPlan &p, int64_t *spans) {
-    HV_REQUIRE(lo_host && radix_host && W >= 1 && W <= HIDVAE_PREFIX_MAX_W, "prefix: %d indexed columns (1 .. %d)", W, HIDVAE_PREFIX_MAX_W);
-    p = PrefixPlan{};
-    int64_t prod = 1;
-    for (int j = W - 1; j >= 0; j--) {
-        HV_REQUIRE(radix_host[j] >= 1 && lo_host[j] <= 0, "prefix: column %d has radix %lld, offset %lld (radix >= 1, offset <= 0)", j,
-                   (long long)radix_host[j], (long long)lo_host[j]);
-        HV_REQUIRE(prod <= (HIDVAE_PREFIX_KEY_LIMIT - 1) / radix_host[j], "prefix: the radix product of %d columns reaches 2^62", W);
-        spans[j + 1] = prod;
-        prod *= radix_host[j];
-        p.lo[j] = lo_host[j];
-        p.radix[j] = radix_host[j];
-    }
-    spans[0] = prod;
-    return HIDVAE_OK;
 }
 
 }  // namespace

@@ -1,21 +1,29 @@
 """HSemanticIdTokenizer on the HIP path (reference modules/tokenizer/h_semids.py:24-532): owns an eval-mode HRqVae,
 turns item features into semantic-id tuples (optionally concatenated / interleaved with predicted tag ids), caches the
 corpus ids and answers prefix queries for constrained decoding: does a prefix exist (`exists_prefix`), and which ids may follow it
-(`valid_next_ids`, not in the reference).
+(`valid_next_ids`, not in the reference), and takes one constrained beam-search step on them in one launch (`beam_step`).
 
 Differences in HOW (not what): the corpus is encoded in large resident chunks through the fused encode + RQ kernels
 instead of 512-item DataLoader batches, and the prefix queries are binary searches in one sorted-key index per cache (built on
 first use, prefix_index.py; one launch per call) instead of a [queries, corpus, L] broadcast compare."""
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor, nn
 
+from ... import _C
 from ...data.schemas import SeqBatch, TokenizedSeqBatch
 from ..h_rqvae import HRqVae
 from .prefix_index import BATCH_SIZE, PrefixIndex, position_vocab  # noqa: F401  (BATCH_SIZE: the reference's module constant)
 
 CORPUS_CHUNK = 65536
+
+
+class BeamStep(NamedTuple):
+    sem_ids: Tensor     # [B, k, i + 1] int64: the parent's ids followed by the chosen id
+    log_probas: Tensor  # [B, k] fp32, best first
+    parents: Tensor     # [B, k] int64: the parent beam j of each entry
+    valid: Tensor       # [B, k] bool: does the entry start some cached item (False: it carries the -10000 penalty)
 
 
 def _eval_mode(fn):
@@ -177,6 +185,78 @@ class HSemanticIdTokenizer(nn.Module):
         if not 0 <= w < W:
             raise ValueError(f"valid_next_ids: prefix width {w}, the cache holds {W} ids per item (the next id needs width < {W})")
         return self._index().next_ids(sem_id_prefix)
+
+    @torch.no_grad()
+    def beam_step(self, logits: Tensor, candidates: Optional[Tensor] = None, generated: Optional[Tensor] = None,
+                  log_probas: Optional[Tensor] = None, k: int = 32, temperature: float = 1.0) -> BeamStep:
+        """One position of the reference's constrained beam search (modules/model.py:200-226) in one launch, without a host
+        synchronisation and with no allocation beyond the four outputs.
+
+        logits [B * k_prev, V] fp32 on the device, the rows of one batch item adjacent (k_prev = 1 when generated is None: position
+        0); candidates [B * k_prev, C] int32 / int64, the ids drawn for each row (the reference: torch.multinomial(probas, 200)), or
+        None for every id 0 .. V-1 in order (C = V, the exhaustive step); generated [B, k_prev, i] int64 and log_probas [B, k_prev]
+        fp32, the previous step's outputs.  Candidate c of parent j scores (-10000 * (not valid) + logp) + log_probas[b, j] in this
+        fp32 order, logp the log-softmax of logits / temperature at the candidate's id, valid iff generated[b, j] followed by the id
+        starts some cached item (an id outside [0, V) is invalid and has logp = -inf).  Returned: the k best of the k_prev * C
+        candidates of each batch item, best first, ties towards the lower flat index j * C + c.  A penalised candidate is returned when
+        fewer than k valid ones were offered; `valid` tells them apart.
+
+        Two deliberate differences from the reference: every row is checked (the reference's exists_prefix leaves the trailing
+        rows % 16 rows of dimension 0 unexamined, which at position 0 with B % 16 != 0 marks whole batch items invalid), and logp is
+        taken in log-softmax form (x/T - max - log sum exp), finite where the reference's log(softmax(.)) underflows to -inf.
+
+        Limits: 1 <= k <= 64, k_prev <= 64, k <= k_prev * C <= 32768, and i + 1 ids must fit the index (OverflowError, as valid_next_ids)."""
+        if self.cached_ids is None:
+            raise Exception("No match found in empty cache.")
+        if logits.dim() != 2 or logits.shape[0] == 0 or logits.shape[1] == 0:
+            raise ValueError(f"beam_step: expected logits [B * k_prev, V], got shape {tuple(logits.shape)}")
+        rows, V = logits.shape
+        if (generated is None) != (log_probas is None):
+            raise ValueError("beam_step: generated and log_probas come together (both None at position 0)")
+        k_prev, i = 1, 0
+        if generated is not None:
+            if generated.dim() != 3 or generated.shape[-1] == 0 or tuple(log_probas.shape) != tuple(generated.shape[:2]):
+                raise ValueError(f"beam_step: expected generated [B, k_prev, i] and log_probas [B, k_prev], got "
+                                 f"{tuple(generated.shape)} and {tuple(log_probas.shape)}")
+            k_prev, i = generated.shape[1], generated.shape[2]
+            if generated.shape[0] * k_prev != rows:
+                raise ValueError(f"beam_step: {rows} logits rows for generated {tuple(generated.shape)} (B * k_prev rows)")
+        B = rows // k_prev
+        C = V
+        if candidates is not None:
+            if candidates.dim() != 2 or candidates.shape[0] != rows or candidates.shape[1] == 0:
+                raise ValueError(f"beam_step: expected candidates [{rows}, C], got shape {tuple(candidates.shape)}")
+            if candidates.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"beam_step: candidates are int32 or int64 ids, got {candidates.dtype}")
+            C = candidates.shape[1]
+        if not 1 <= k <= _C.BEAM_MAX_K:
+            raise ValueError(f"beam_step: k = {k} beams (1 .. {_C.BEAM_MAX_K})")
+        if k_prev > _C.BEAM_MAX_K:
+            raise ValueError(f"beam_step: {k_prev} parent beams (the parents are an earlier step's at most {_C.BEAM_MAX_K} beams)")
+        if k_prev * C > _C.BEAM_MAX_CANDIDATES:
+            raise ValueError(f"beam_step: {k_prev} parents x {C} candidates per batch item exceed the {_C.BEAM_MAX_CANDIDATES} the "
+                             f"in-LDS selection holds")
+        if k > k_prev * C:
+            raise ValueError(f"beam_step: k = {k} beams out of {k_prev * C} candidates")
+        if not temperature > 0:
+            raise ValueError(f"beam_step: temperature {temperature} (> 0)")
+        W = self.cached_ids.shape[-1]
+        if i >= W:
+            raise ValueError(f"beam_step: position {i}, the cache holds {W} ids per item")
+        if logits.dtype != torch.float32 or not logits.is_cuda:
+            raise RuntimeError(f"beam_step: expected float32 device logits, got {logits.dtype} on {logits.device}; there is no CPU "
+                               f"fallback")
+        index = self._index()
+        index._check_width(i + 1)
+        if logits.stride(1) != 1 and V > 1:
+            logits = logits.contiguous()
+        if candidates is not None:
+            candidates = index._rows(candidates)
+        if generated is not None:
+            generated = index._rows(generated.to(torch.int64))
+            log_probas = log_probas.to(device=logits.device, dtype=torch.float32).reshape(-1)
+        out = _C.beam_step(logits, candidates, generated, log_probas, B, int(k), float(temperature), index.plan, index.keys)
+        return BeamStep(*out)
 
     # ------------------------------------------------------------------------------------------------
     def _tokenize_seq_batch_from_cached(self, ids: Tensor) -> Tensor:

@@ -621,6 +621,24 @@ int hidvae_prefix_exists(const void *q, int q_bytes, int64_t n_q, int64_t ldq, i
 int hidvae_prefix_next(const void *q, int q_bytes, int64_t n_q, int64_t ldq, int w, const int64_t *lo_host, const int64_t *radix_host,
                        int W, const int64_t *keys, int64_t n_keys, int64_t V, uint8_t *out, void *stream);
 
+/* model.py:200-226 (one position of generate_next_sem_id's loop) in one launch (csrc/beam.hip).  Batch item b has k_prev parent beams,
+ * rows b * k_prev + j of logits [B * k_prev, V] (row stride ld_logits), of cand [B * k_prev, C] (cand_bytes 4: int32, 8: int64, row stride
+ * ldc; cand_bytes 0: candidate c IS id c and C = V), of generated [B * k_prev, w] (the parents' ids, row stride ldg; unread at w = 0) and
+ * of log_probas [B * k_prev] (NULL: zeros).  Candidate c of parent j scores (-10000 * (not valid) + logp) + log_probas in this fp32
+ * order, logp = (x[id] / temperature - max) - log sum exp, valid iff the parent's w ids followed by id are the first w + 1 columns of
+ * some indexed row (an id outside [0, V) is invalid with logp = -inf; a parent with an entry outside the plan makes all its candidates
+ * invalid).  Out, per batch item, the k best by (score descending, flat index j * C + c ascending): out_ids [B, k, w + 1] (parent ids,
+ * then the id), out_logp [B, k] (the score), out_parents [B, k] (j), out_valid [B, k] (torch.bool bytes, the candidate's own validity).
+ * 1 <= k <= HIDVAE_BEAM_MAX_K, k_prev <= HIDVAE_BEAM_MAX_K (the parents are an earlier step's beams), k <= k_prev * C <=
+ * HIDVAE_BEAM_MAX_CANDIDATES (the scores of a batch item are selected in LDS), 0 <= w < W.
+ * No workspace, no host synchronisation. */
+#define HIDVAE_BEAM_MAX_K 64
+#define HIDVAE_BEAM_MAX_CANDIDATES 32768
+int hidvae_beam_step(const float *logits, int64_t ld_logits, int64_t B, int64_t k_prev, int64_t V, const void *cand, int cand_bytes,
+                     int64_t ldc, int64_t C, const int64_t *generated, int64_t ldg, const float *log_probas, int w, int k, float temperature,
+                     const int64_t *lo_host, const int64_t *radix_host, int W, const int64_t *keys, int64_t n_keys, int64_t *out_ids,
+                     float *out_logp, int64_t *out_parents, uint8_t *out_valid, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,10 +99,11 @@ _SIGNATURES = {
     "hidvae_prefix_next": [_vp, _i, _i64, _i64, _i, _vp, _vp, _i, _vp, _i64, _i64, _vp, _vp],
     "hidvae_beam_step": [_vp, _i64, _i64, _i64, _i64, _vp, _i, _i64, _i64, _vp, _i64, _vp, _i, _i, _f, _vp, _vp, _i, _vp, _i64, _vp, _vp, _vp,
                          _vp, _vp],
+    "hidvae_retrieval_metrics": [_vp, _i, _i64, _vp, _i, _i64, _i64, _i64, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 WS_GEMM, WS_LINEAR_BWD, WS_COLSUM, WS_CODEBOOK_GRAD, WS_LAYERNORM_PARAM_GRAD, WS_LAYERNORM_BWD_ALL = 1, 2, 3, 4, 5, 6
 WS_BATCHNORM_FWD, WS_BATCHNORM_BWD, WS_ID_CENSUS, WS_KMEANS, WS_TAG_LOSS, WS_LINEAR_BWD_ZEROED, WS_RQ_FORWARD = 7, 8, 9, 10, 11, 12, 13
-WS_LINEAR_BWD_BF16, WS_GEMM_BF16, WS_BF16_ZEROED = 14, 15, 16
+WS_LINEAR_BWD_BF16, WS_GEMM_BF16, WS_BF16_ZEROED, WS_RETRIEVAL_METRICS = 14, 15, 16, 17
 PRECISIONS = ("fp32", "bf16")  # operand precision of the Linear entry points (bf16: the amp mode's kernels)
 
 
@@ -1518,3 +1519,30 @@ def beam_step(logits, candidates, generated, log_probas, B, k, temperature, plan
                                   float(temperature), plan.lo, plan.radix, plan.W, _p(keys), keys.numel(), _p(ids), _p(logp), _p(parents),
                                   _p(valid), _stream()), "hidvae_beam_step")
     return ids, logp, parents, valid
+
+
+METRICS_MAX_D, METRICS_MAX_KS = 8, 8
+METRICS_HITS, METRICS_NDCG = 1, 2
+METRICS_SLOTS = 2 * METRICS_MAX_D * METRICS_MAX_KS  # entries of either state: [kind (slice, position)][i][kidx]
+
+
+def _id_rows(t, name):
+    if not t.is_cuda or t.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError(f"retrieval_metrics: expected int32 / int64 device ids for {name}, got {t.dtype} on {t.device}")
+    if t.shape[-1] > 1 and t.stride(-1) != 1:
+        raise RuntimeError(f"retrieval_metrics: the last dimension of {name} must be contiguous (strides {t.stride()})")
+
+
+def retrieval_metrics(actual, top_k, ks, flags, discounts, hits, ndcg, rows, workspace):
+    """hit@k / NDCG@k of one batch added onto the caller's state (hidvae_retrieval_metrics, one launch, nothing read back): actual
+    [B, D] and top_k [B, K, D] int32 / int64 device ids, any row and beam strides; ks: a ctypes int32 array; discounts: float64 [129]
+    on the device; hits int64 [128], ndcg float64 [128], rows int64 [1]; workspace: WS_RETRIEVAL_METRICS bytes, leading 8 zero"""
+    _id_rows(actual, "actual"), _id_rows(top_k, "top_k")
+    B, K, D = top_k.shape
+    if tuple(actual.shape) != (B, D):
+        raise RuntimeError(f"retrieval_metrics: actual {tuple(actual.shape)} against top_k {tuple(top_k.shape)}")
+    if ndcg is not None and workspace.numel() * workspace.element_size() < workspace_bytes(WS_RETRIEVAL_METRICS, B):
+        raise RuntimeError("retrieval_metrics: the workspace is smaller than hidvae_query_workspace asks for")
+    _check(lib().hidvae_retrieval_metrics(_p(actual), actual.element_size(), actual.stride(0), _p(top_k), top_k.element_size(),
+                                          top_k.stride(0), top_k.stride(1), int(B), int(K), int(D), ks, len(ks), int(flags), _p(discounts),
+                                          _p(hits), _p(ndcg), _p(rows), _p(workspace), _stream()), "hidvae_retrieval_metrics")

@@ -96,11 +96,12 @@ _DROPIN = {
     "init.kmeans": "init.kmeans", "data.schemas": "data.schemas", "data.utils": "data.utils",
     "distributions.gumbel": "distributions.gumbel",
     "ops.triton.jagged": "ops_hip.jagged",  # (stage-2 imports padded_to_jagged_tensor)
+    "evaluate.metrics": "evaluate.metrics",  # (stage-2 evaluation: TopKAccumulator, NDCGAccumulator)
 }
 # parent package -> the mirror package that stands in for it when the reference tree is NOT importable (then nothing
 # un-mirrored could be resolved anyway)
 _PARENT_FALLBACK = {"modules": "modules", "modules.tokenizer": "modules.tokenizer", "init": "init", "data": "data",
-                    "distributions": "distributions", "ops": "ops_hip", "ops.triton": "ops_hip"}
+                    "distributions": "distributions", "ops": "ops_hip", "ops.triton": "ops_hip", "evaluate": "evaluate"}
 
 
 def _dropin_parent(name):

@@ -59,6 +59,13 @@ extern "C" int hidvae_query_workspace(int op, const int64_t *d, int n, int64_t *
     case HIDVAE_WS_RQ_FORWARD: if (need(3)) fl = d[0] >= 65536 ? d[0] + 4 : 0; break;                       // B, L, K  (counter + item list)
     case HIDVAE_WS_KMEANS: if (need(2)) fl = d[1]; break;                                               // N, K
     case HIDVAE_WS_TAG_LOSS: if (need(2)) fl = 2 * d[0] + d[0] * d[1]; break;                           // B, C  (row_loss, row_hit, zbuf)
+    case HIDVAE_WS_RETRIEVAL_METRICS: {  // B: the arrival counter (8 bytes), then one partial per state entry per workgroup
+        if (!need(1)) break;
+        int64_t g = cdiv(d[0], HIDVAE_METRICS_ROWS_PER_BLOCK);
+        g = g < 1 ? 1 : (g > HIDVAE_METRICS_MAX_BLOCKS ? HIDVAE_METRICS_MAX_BLOCKS : g);
+        *bytes = 8 + g * 2 * HIDVAE_METRICS_MAX_D * HIDVAE_METRICS_MAX_KS * 8;
+        return HIDVAE_OK;
+    }
     default: return hv_fail(HIDVAE_EINVAL, "query_workspace: unknown op %d", op);
     }
     if (fl < 0) return hv_fail(HIDVAE_EINVAL, "query_workspace: op %d needs more dimensions than %d", op, n);

@@ -87,6 +87,10 @@ const char *hidvae_last_error(void);
 #define HIDVAE_WS_BF16_ZEROED 16         /* (no dimensions needed)    -> leading bytes of either bf16 workspace that must be ZERO on entry
                                             (arrival counters; left zero on return): the contract of HIDVAE_WS_LINEAR_BWD_ZEROED, at every
                                             shape.  One buffer per stream serves the fp32 and the bf16 entries alike. */
+#define HIDVAE_WS_RETRIEVAL_METRICS 17    /* B                         -> hidvae_retrieval_metrics workspace: 8 + min(max(ceil(B/16), 1), 128) * 128 * 8
+                                            bytes, whose leading 8 bytes (the arrival counter) must be ZERO on entry and are zero again on
+                                            return; never shared with a launch that may run at the same time.  The size at B >= 2048 serves
+                                            every B. */
 int hidvae_query_workspace(int op, const int64_t *dims, int n_dims, int64_t *bytes);
 
 /* ---- a2/a3/a9/a10: Linear layers (modules/encoder.py:23-36, h_rqvae.py:132-188,322-331) ------------
@@ -638,6 +642,34 @@ int hidvae_beam_step(const float *logits, int64_t ld_logits, int64_t B, int64_t 
                      int64_t ldc, int64_t C, const int64_t *generated, int64_t ldg, const float *log_probas, int w, int k, float temperature,
                      const int64_t *lo_host, const int64_t *radix_host, int W, const int64_t *keys, int64_t n_keys, int64_t *out_ids,
                      float *out_logp, int64_t *out_parents, uint8_t *out_valid, void *stream);
+
+/* ---- stage-2 evaluation: hit@k and NDCG@k of generated semantic ids (reference evaluate/metrics.py:17-30 TopKAccumulator.accumulate,
+ * :63-91 NDCGAccumulator.accumulate) in ONE launch (csrc/metrics.hip).  actual [B, D] (row stride lda) and top_k [B, K, D] (row stride
+ * ld_row, beam stride ld_beam), int32 (bytes 4) or int64 (8) each, the last dimension contiguous: a [..., :D] view of wider tensors
+ * costs no copy.  Ids are compared as integers and never used as an index.  For every predicate -- slice :i+1 (kind 0: beam j repeats
+ * the first i + 1 ids of actual) and position i (kind 1: it repeats id i), i < D -- a row's matching beams are a K-bit set `mask`; with
+ * first = ctz(mask), m = popcount(mask), disc[j] = 1 / log2(j + 2), for every k = ks_host[kidx]:
+ *     hits[kind][i][kidx] += (mask != 0 and first < k)                                                     (int64, [2][8][8])
+ *     ndcg[kind][i][kidx] += sum_{j < k, j in mask} disc[j] / sum_{j < min(m, k)} disc[j]   (0 at m = 0)    (float64, [2][8][8])
+ * the NDCG term only for k <= K (the reference skips k > K; a hit at k > K counts every match), and rows[0] += B.  The state is the
+ * caller's, zero-filled once; entries of i >= D or kidx >= nk are left alone, so successive calls may differ in D and K.
+ *   flags      HIDVAE_METRICS_HITS | HIDVAE_METRICS_NDCG: which of the two states is updated (the other pointer may be NULL)
+ *   discounts  device float64 [129], computed by the caller on the host: disc[0 .. 64), then cum[n] = disc[0] + ... + disc[n - 1] in
+ *              this order, n = 0 .. 64 (NDCG only).  The kernel evaluates no transcendental.
+ *   workspace  hidvae_query_workspace(HIDVAE_WS_RETRIEVAL_METRICS, {B}) bytes (NDCG only), leading 8 bytes zero on entry and on return
+ * Reproducible: no floating-point atomics; the float64 sums are added in a fixed order (rows ascending per wave, waves, then
+ * workgroups in index order by the one that arrives last), so equal inputs on an equal state give a bit-identical state.
+ * 1 <= K <= HIDVAE_BEAM_MAX_K, 1 <= D <= HIDVAE_METRICS_MAX_D, 1 <= nk <= HIDVAE_METRICS_MAX_KS, every k >= 1.  No host
+ * synchronisation, no allocation; capturable in a HIP graph. */
+#define HIDVAE_METRICS_MAX_D 8
+#define HIDVAE_METRICS_MAX_KS 8
+#define HIDVAE_METRICS_HITS 1
+#define HIDVAE_METRICS_NDCG 2
+#define HIDVAE_METRICS_ROWS_PER_BLOCK 16 /* batch rows a workgroup works on at a time (one wave each) */
+#define HIDVAE_METRICS_MAX_BLOCKS 128    /* workgroups of a launch at the most: the partials the last one adds up */
+int hidvae_retrieval_metrics(const void *actual, int actual_bytes, int64_t lda, const void *top_k, int top_k_bytes, int64_t ld_row,
+                             int64_t ld_beam, int64_t B, int K, int D, const int32_t *ks_host, int nk, int flags, const double *discounts,
+                             int64_t *hits, double *ndcg, int64_t *rows, void *workspace, void *stream);
 
 #ifdef __cplusplus
 }

@@ -932,8 +932,9 @@ def mul(a, b):
 
 
 def sum_prefix_slices(srcs, M, N):
-    """srcs: list of contiguous [M, w_i] tensors (or None) -> dst [M, N] with each added into the first w_i columns."""
-    live = [t for t in srcs if t is not None]
+    """srcs: list of [M, w_i] tensors (or None) -> dst [M, N] with each added into the first w_i columns.  The kernel reads rows at
+    stride w_i: a view with another row stride is copied first."""
+    live = [t if t.is_contiguous() else t.contiguous() for t in srcs if t is not None]
     dst = torch.empty((M, N), device=live[0].device, dtype=torch.float32)
     ptrs = (ctypes.c_void_p * len(live))(*[t.data_ptr() for t in live])
     widths = (ctypes.c_int32 * len(live))(*[t.shape[1] for t in live])

@@ -247,9 +247,8 @@ __global__ __launch_bounds__(64 * PRED_WAVES) void predictor_fwd_kernel(PredArgs
             Hout[t * 64 + lane] = val[s];
             if (u.residual || u.carry) img[res][t * 64 + lane] = val[s];
         }
-        // (tiles past ntile of the NEXT unit's k range must read as zero: a narrower output leaves stale blocks behind)
-        const int nkb_next = ui + 1 < a.n ? (a.u[ui + 1].K + 15) / 16 : 0;
-        for (int t = ntile + wave; t < nkb_next; t += PRED_WAVES) Hout[t * 64 + lane] = make_float4(0.f, 0.f, 0.f, 0.f);
+        // (the next unit reads k blocks [0, ceil(K / 16)) with K == N -- the entry point refuses any other list -- which are exactly the
+        //  ntile tiles written above, columns past N as zeros: a narrower unit's stale blocks further up are never read)
         __syncthreads();
         cur ^= 1;
     }
@@ -312,7 +311,10 @@ __global__ __launch_bounds__(64 * PRED_WAVES) void predictor_bwd_kernel(PredArgs
                 const float4 r4 = img[2][t * 64 + lane];
                 gv.x += r4.x; gv.y += r4.y; gv.z += r4.z; gv.w += r4.w;
             }
-            if (u.residual) img[2][t * 64 + lane] = gv;  // (own slot: read above by this lane only)
+            // (own slot: read above by this lane only.)  A carry unit that is no residual unit STARTS the carried residual: what was
+            // carried in front of it never reaches a later unit, so no gradient travels past it on the residual path
+            if (u.residual) img[2][t * 64 + lane] = gv;
+            else if (u.carry) img[2][t * 64 + lane] = make_float4(0.f, 0.f, 0.f, 0.f);
             const f32x4 l4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rl, off, 0, 0));
             const f32x4 y4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ry, off, 0, 0));
             const f32x4 ga = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rg, 4 * col0, 0, 0));
@@ -441,12 +443,27 @@ __global__ __launch_bounds__(64 * PRED_WAVES) void predictor_bwd_kernel(PredArgs
     }
 }
 
+// A residual unit adds the carried residual: one must exist (an earlier carry or residual unit wrote it) and be as wide as this unit.
+// -> the index of the first unit that breaks the rule, or -1
+int pred_residual_chain_error(const hidvae_pred_unit *units, int n_units) {
+    int carried = 0;  // width of the carried residual, 0: none yet
+    for (int i = 0; i < n_units; i++) {
+        if (units[i].residual && carried != units[i].N) return i;
+        if (units[i].residual || units[i].carry) carried = units[i].N;
+    }
+    return -1;
+}
+
 }  // namespace
 
 extern "C" int hidvae_predictor_fwd(const float *h, int64_t ldh, int64_t B, const hidvae_pred_unit *units, int n_units,
                                     const unsigned long long *rng_state, void *stream) {
     HV_REQUIRE(h && units && B >= 1 && n_units >= 1 && n_units <= PRED_MAX_UNITS, "predictor_fwd: bad arguments");
     HV_REQUIRE(B <= (int64_t)1 << 20, "predictor_fwd: B=%lld (byte offsets are 32-bit)", (long long)B);
+    {
+        const int bad = pred_residual_chain_error(units, n_units);
+        HV_REQUIRE(bad < 0, "predictor_fwd: unit %d: residual without a carried residual of its width %d (an earlier carry / residual unit)", bad, bad >= 0 ? units[bad].N : 0);
+    }
     PredArgs a{};
     a.h = h; a.B = B; a.ldh = ldh; a.n = n_units; a.rng = rng_state;
     for (int i = 0; i < n_units; i++) {
@@ -456,6 +473,7 @@ extern "C" int hidvae_predictor_fwd(const float *h, int64_t ldh, int64_t B, cons
         HV_REQUIRE(i == 0 ? ldh >= s.K : s.K == units[i - 1].N, "predictor_fwd: unit %d does not continue unit %d", i, i - 1);
         HV_REQUIRE(s.gamma == nullptr || (s.beta && s.y && s.mean && s.rstd), "predictor_fwd: unit %d: LayerNorm outputs missing", i);
         HV_REQUIRE(s.gamma != nullptr || (!s.act2 && !s.residual), "predictor_fwd: unit %d: act2 / residual need the LayerNorm", i);
+        HV_REQUIRE(!(s.act2 && s.residual), "predictor_fwd: unit %d: act2 with residual (the backward reads the act2 gate off the saved output, which would hold the residual too)", i);
         HV_REQUIRE((s.drop_threshold1 == 0u && s.drop_threshold2 == 0u) || rng_state != nullptr, "predictor_fwd: unit %d: dropout needs the generator state", i);
         PredUnit &u = a.u[i];
         u.W = s.W; u.bias = s.bias; u.gamma = s.gamma; u.beta = s.beta; u.N = s.N; u.K = s.K;
@@ -473,6 +491,10 @@ extern "C" int hidvae_predictor_bwd(const float *g_out, int64_t ldg, int64_t B, 
                                     int64_t ldgh, void *stream) {
     HV_REQUIRE(g_out && units && g_h && B >= 1 && n_units >= 1 && n_units <= PRED_MAX_UNITS, "predictor_bwd: bad arguments");
     HV_REQUIRE(B <= (int64_t)1 << 20, "predictor_bwd: B=%lld (byte offsets are 32-bit)", (long long)B);
+    {
+        const int bad = pred_residual_chain_error(units, n_units);
+        HV_REQUIRE(bad < 0, "predictor_bwd: unit %d: residual without a carried residual of its width %d (an earlier carry / residual unit)", bad, bad >= 0 ? units[bad].N : 0);
+    }
     PredArgs a{};
     a.B = B; a.n = n_units;
     for (int i = 0; i < n_units; i++) {
@@ -481,6 +503,7 @@ extern "C" int hidvae_predictor_bwd(const float *g_out, int64_t ldg, int64_t B, 
         HV_REQUIRE(i == 0 || s.K == units[i - 1].N, "predictor_bwd: unit %d does not continue unit %d", i, i - 1);
         HV_REQUIRE(s.gamma == nullptr || (s.y && s.mean && s.rstd && s.partials), "predictor_bwd: unit %d: LayerNorm tensors missing", i);
         HV_REQUIRE(s.gamma != nullptr || (!s.act2 && !s.residual), "predictor_bwd: unit %d: act2 / residual need the LayerNorm", i);
+        HV_REQUIRE(!(s.act2 && s.residual), "predictor_bwd: unit %d: act2 with residual (the backward reads the act2 gate off the saved output, which would hold the residual too)", i);
         PredUnit &u = a.u[i];
         u.W = s.W; u.gamma = s.gamma; u.N = s.N; u.K = s.K;
         u.act1 = s.act1; u.act2 = s.act2; u.residual = s.residual; u.carry = s.carry;

@@ -306,8 +306,9 @@ int hidvae_l2norm_bwd_pair(const float *g0, int64_t ldg0, const float *out0, con
 
 /* ---- a12: SemanticIdUniquenessLoss exactly as HRqVae.forward calls it (h_rqvae.py:41-105 with the [L,B]
  * transposed ids of :630-631): level pairs (a<b) whose id vectors agree over the whole batch contribute
- * relu(cos(z[a], z[b]) - margin); loss = weight * mean over such pairs (0 if none).  g_rows [L,32] (optional) receives
- * d loss / d z[0:L].  a1: total loss = mean(recon)+mean(qloss)+w_a*align+w_p*pred+w_u*uniq (h_rqvae.py:634-640),
+ * relu(cos(z[a], z[b]) - margin); loss = weight * mean over such pairs (0 if none).  A flagged pair with b >= B has no row z[b] (the
+ * reference raises IndexError there): it contributes nothing and still counts in the mean.  g_rows [L,32] (optional) receives
+ * d loss / d z[0:L] (rows past B: 0).  a1: total loss = mean(recon)+mean(qloss)+w_a*align+w_p*pred+w_u*uniq (h_rqvae.py:634-640),
  * the uniqueness term evaluated in the same launch when ids != NULL.  align/pred/acc: HOST arrays of n_tag per-level
  * device scalars (n_tag = 0 for an untagged batch); tag_align = sum_i align_i / tag_div etc. (h_rqvae.py:561-563);
  * tagstats [3+3*n_tag] (optional) receives the three means followed by the three by-layer vectors; summary [6] (optional)
@@ -331,8 +332,8 @@ int hidvae_total_loss_bwd(const float *g_loss, int64_t B, int L, float w_a, floa
  * loss_bwd: g_y = (g_loss/B) d recon/d y;  scal / g_z exactly as hidvae_total_loss_bwd.
  * n_cat: categorical columns at the end of the row, as in hidvae_recon_fwd_bwd (0 on every shipped config).
  * expect_g (loss_bwd; 0 = no check): the loss gradient part of the backward was already seeded with (the tag heads' early backward,
- *   hidvae_amd/tagpath.py HeadsGradPort); if *g_loss differs, every output of the launch is NaN -- the step fails visibly instead of
- *   mixing two scalings. */
+ *   hidvae_amd/tagpath.py HeadsGradPort); if *g_loss differs, every gradient the launch writes is NaN (g_y, scal, the first L rows of
+ *   g_z; the rows of g_z past L carry no gradient and stay 0) -- the step fails visibly instead of mixing two scalings. */
 int hidvae_loss_fwd(const float *y, const float *x, int64_t B, int64_t N, int n_cat, const float *qloss,
                     const float *const *align_host, const float *const *pred_host, const float *const *acc_host, int n_tag,
                     float tag_div, const int64_t *ids, const float *z, int L, float uniq_weight, float uniq_margin, float w_a,
@@ -458,7 +459,11 @@ int hidvae_layernorm_param_final_many(const hidvae_ln_final *problems_host, int 
  * receives what the separate launches would save as the LayerNorm's input / the Linear's output (after ReLU -> Dropout(1) if act1),
  * `y`, `mean`, `rstd` the LayerNorm's outputs -- so hidvae_linear_bwd / hidvae_layernorm_bwd_partial run the backward unchanged.
  * carry: the unit's output becomes the carried residual; residual: the carried residual is added after the LayerNorm and the sum
- * becomes the new carried residual.  Dropout decisions: the counter-based generator on element index row * N + col of the given site
+ * becomes the new carried residual; a carry unit that is no residual unit starts the carried residual afresh (what was carried in front of
+ * it reaches no later unit).  A residual unit needs a carried residual of its own width: an earlier carry or residual unit must
+ * exist and the latest of them must have the same N -- both entry points refuse a list that breaks this (HIDVAE_EINVAL), as they
+ * refuse act2 / residual on a unit without a LayerNorm, and act2 together with residual on one unit (the backward reads the
+ * ReLU -> Dropout(2) gate off the saved output y > 0, and y would hold the residual too).  Dropout decisions: the counter-based generator on element index row * N + col of the given site
  * (threshold 0: no dropout), exactly as hidvae_gemm_f32 / hidvae_layernorm_fwd take them. */
 typedef struct {
     const float *W, *bias, *gamma, *beta;

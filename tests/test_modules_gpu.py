@@ -341,12 +341,23 @@ def test_softmax_argmax_rows_is_torchs_softmax_max():
         assert (pred[:, 0] == -7).all() and (pred[:, 2] == -7).all() and (conf[:, 0] == -7).all() and (conf[:, 2] == -7).all()
 
 
-@pytest.mark.parametrize("E,H,C,layer_idx,B,p", [(32, 256, 38, 0, 1024, 0.4), (64, 128, 17, 1, 100, 0.25), (96, 250, 348, 2, 37, 0.0)])
-def test_one_launch_predictor_forward_matches_the_separate_launches(E, H, C, layer_idx, B, p):
+@pytest.mark.parametrize("E,H,C,layer_idx,B,p", [(32, 256, 38, 0, 1024, 0.4), (64, 128, 17, 1, 100, 0.25), (96, 250, 348, 2, 37, 0.0),
+                                                 (96, 250, 200, 2, 37, 0.0), (128, 256, 256, 2, 1000, 0.3)])
+def test_one_launch_predictor_forward_matches_the_separate_launches(E, H, C, layer_idx, B, p, monkeypatch):
     """hidvae_predictor_fwd (TagPredictor behind its gate as ONE row-local launch, reference h_rqvae.py:132-188) against the launch
     sequence it replaces, under the SAME in-kernel dropout decisions: the logits, the input gradient and every parameter gradient
-    (the backward is the same Functions either way; only what they were handed differs in summation order of the LayerNorms)."""
+    (the backward is the same Functions either way; only what they were handed differs in summation order of the LayerNorms).
+    Every run asserts the path it took by counting the calls of _C.predictor_fwd / _C.predictor_bwd.  The set with 348 classes is
+    wider than the launch's 256 columns: it is the UNFUSED FALLBACK compared with itself, and holds only that asking for the
+    one-launch path where it does not apply changes nothing."""
     import os
+    from hidvae_amd import _C
+    fuses = max(E, H, C) <= 256  # no layer wider than the launch keeps in LDS
+    assert fuses == ((E, H, C) != (96, 250, 348))
+    calls = {"fwd": 0, "bwd": 0}
+    real_fwd, real_bwd = _C.predictor_fwd, _C.predictor_bwd
+    monkeypatch.setattr(_C, "predictor_fwd", lambda *a, **k: (calls.__setitem__("fwd", calls["fwd"] + 1), real_fwd(*a, **k))[1])
+    monkeypatch.setattr(_C, "predictor_bwd", lambda *a, **k: (calls.__setitem__("bwd", calls["bwd"] + 1), real_bwd(*a, **k))[1])
     from hidvae_amd.modules.h_rqvae import TagPredictor
     from hidvae_amd.rand import DeviceRand
     from hidvae_amd.tagpath import tag_predictor_forward, flush_layernorm_finals
@@ -379,9 +390,12 @@ def test_one_launch_predictor_forward_matches_the_separate_launches(E, H, C, lay
             os.environ.pop("HIDVAE_FUSED_PREDICTOR_BWD", None)
 
     lu, gxu, gpu = run(False)
+    assert calls == {"fwd": 0, "bwd": 0}, calls
     rel = lambda a, b: float((a - b).abs().max()) / max(1e-6, float(b.abs().max()))
     for bwd in (False, True):  # the one-launch forward under the separate backward launches, then with the one-launch backward too
+        calls.update(fwd=0, bwd=0)
         lf, gxf, gpf = run(True, bwd)
+        assert calls == {"fwd": int(fuses), "bwd": int(fuses and bwd)}, (bwd, calls)
         assert rel(lf, lu) <= 1e-5, (bwd, rel(lf, lu))
         assert rel(gxf, gxu) <= 2e-5, (bwd, rel(gxf, gxu))
         for n in gpu:

@@ -80,6 +80,7 @@ _SIGNATURES = {
     "hidvae_padded_to_jagged": [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp],
     "hidvae_jagged_to_padded": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp],
     "hidvae_gather_rows": [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp],
+    "hidvae_jagged_attention_fwd": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i, _i, _i, _i, _f, _vp],
     "hidvae_codebook_prepare_adamw": [_vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _i64, _i64, _f, _vp, _i, _vp],
     "hidvae_adamw_prepare": [_vp, _vp, _vp, _i, _f, _f, _f, _i64, _i64, _f, _vp, _vp],
     "hidvae_adamw_step": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _f, _f, _f, _f, _vp],
@@ -1398,6 +1399,46 @@ def jagged_to_padded(values, offsets, B, N):
     _check(lib().hidvae_jagged_to_padded(ctypes.c_void_p(values.data_ptr()), _p(offsets), _p(x), N * D * es, D * es, B, N, D * es, _stream()),
            "hidvae_jagged_to_padded")
     return x
+
+
+ATTENTION_HEAD_DIMS = (32, 64, 128)
+
+
+def jagged_attention(q, k, v, q_offsets, kv_offsets, num_heads, kv_group=1, causal=False, scale=None, out=None):
+    """hidvae_jagged_attention_fwd: q [total_q, H*Dh], k, v [total_kv, H*Dh] (fp32 device, last dim contiguous, any row stride that is a
+    multiple of 4: column-chunk views of packed qkv / kv matrices cost no copy), offsets int64 device [n + 1] -> out [total_q, H*Dh].
+    Every check here reads shape metadata only; forward only (no autograd graph is recorded)."""
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        if not t.is_cuda:
+            raise RuntimeError(f"jagged_attention: {name} is a CPU tensor; hidvae HIP kernels need device tensors (there is no CPU fallback)")
+        _f32(t, f"jagged_attention: {name}")
+    for t, name in ((q_offsets, "q_offsets"), (kv_offsets, "kv_offsets")):
+        if not t.is_cuda or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous():
+            raise RuntimeError(f"jagged_attention: {name} must be a contiguous int64 device vector, got {t.dtype} on {t.device}")
+    if q.dim() != 2 or k.dim() != 2 or v.dim() != 2 or k.shape != v.shape or q.shape[1] != k.shape[1]:
+        raise RuntimeError(f"jagged_attention: expected q [Tq, d], k and v [Tkv, d], got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    d = q.shape[1]
+    if num_heads < 1 or d % num_heads:
+        raise RuntimeError(f"jagged_attention: width {d} is not divisible by {num_heads} heads")
+    head_dim = d // num_heads
+    if head_dim not in ATTENTION_HEAD_DIMS:
+        raise RuntimeError(f"jagged_attention: head_dim {head_dim} is not one of {ATTENTION_HEAD_DIMS}")
+    nq, nkv = q_offsets.shape[0] - 1, kv_offsets.shape[0] - 1
+    if nq < 1 or nkv < 1 or kv_group < 1 or nq != nkv * kv_group:
+        raise RuntimeError(f"jagged_attention: {nq} query sequences are not {nkv} kv sequences x kv_group {kv_group}")
+    if causal and kv_group != 1:
+        raise RuntimeError(f"jagged_attention: causal attention needs kv_group == 1 (got {kv_group})")
+    if out is None:
+        out = torch.empty((q.shape[0], d), device=q.device, dtype=torch.float32)
+    elif tuple(out.shape) != (q.shape[0], d):
+        raise RuntimeError(f"jagged_attention: out has shape {tuple(out.shape)}, expected {(q.shape[0], d)}")
+    _f32(out, "jagged_attention: out")
+    scale = float(head_dim) ** -0.5 if scale is None else float(scale)
+    _check(lib().hidvae_jagged_attention_fwd(_p(q), _row_stride(q, "q"), _p(k), _row_stride(k, "k"), _p(v), _row_stride(v, "v"), _p(out),
+                                             _row_stride(out, "out"), _p(q_offsets), nq, q.shape[0], _p(kv_offsets), nkv, k.shape[0],
+                                             num_heads, head_dim, kv_group, int(bool(causal)), scale, _stream()),
+           "hidvae_jagged_attention_fwd")
+    return out
 
 
 GATHER_MAX = 4

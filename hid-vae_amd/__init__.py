@@ -88,7 +88,7 @@ from . import _C  # noqa: F401,E402
 
 # reference module name -> mirror module in this package.  Only LEAF modules are replaced: the reference's own parent packages
 # (`modules`, `data`, `init`, `ops`, ...) stay what they are, so everything that is not mirrored (modules.utils, modules.model,
-# modules.transformer.*, data.tags_processed, ...) still resolves to the reference's files.
+# modules.transformer.model, data.tags_processed, ...) still resolves to the reference's files.
 _DROPIN = {
     "modules.h_rqvae": "modules.h_rqvae", "modules.rqvae": "modules.rqvae", "modules.encoder": "modules.encoder",
     "modules.quantize": "modules.quantize", "modules.loss": "modules.loss", "modules.normalize": "modules.normalize",
@@ -97,11 +97,13 @@ _DROPIN = {
     "distributions.gumbel": "distributions.gumbel",
     "ops.triton.jagged": "ops_hip.jagged",  # (stage-2 imports padded_to_jagged_tensor)
     "evaluate.metrics": "evaluate.metrics",  # (stage-2 evaluation: TopKAccumulator, NDCGAccumulator)
+    "modules.transformer.attention": "modules.transformer.attention",  # (stage-2 transformer: Attend, MultiHeadAttention)
 }
 # parent package -> the mirror package that stands in for it when the reference tree is NOT importable (then nothing
 # un-mirrored could be resolved anyway)
 _PARENT_FALLBACK = {"modules": "modules", "modules.tokenizer": "modules.tokenizer", "init": "init", "data": "data",
-                    "distributions": "distributions", "ops": "ops_hip", "ops.triton": "ops_hip", "evaluate": "evaluate"}
+                    "distributions": "distributions", "ops": "ops_hip", "ops.triton": "ops_hip", "evaluate": "evaluate",
+                    "modules.transformer": "modules.transformer"}
 
 
 def _dropin_parent(name):
@@ -124,7 +126,7 @@ def install_dropin(force=False):
     mirrors, so the reference's own scripts and gin files pick up the HIP implementation without edits (INTEGRATION.md,
     section A).  Call it BEFORE importing the reference's scripts.  Only the mirrored leaf modules are replaced (sys.modules entry
     + attribute on the parent package); their parent packages remain the reference's, so `from modules.utils import parse_config`,
-    `modules.model`, `modules.transformer.*` keep working."""
+    `modules.model`, `modules.transformer.model` keep working."""
     for theirs in _DROPIN:
         if theirs in sys.modules and not force and not getattr(sys.modules[theirs], "__name__", "").startswith("hidvae_amd"):
             raise RuntimeError(f"{theirs} is already imported from elsewhere; call install_dropin() before importing the reference")

@@ -598,6 +598,27 @@ int hidvae_padded_to_jagged(const void *x, int64_t stride_b_bytes, int64_t strid
 int hidvae_jagged_to_padded(const void *values, const int64_t *offsets, void *x, int64_t stride_b_bytes, int64_t stride_n_bytes,
                             int64_t B, int64_t N, int64_t row_bytes, void *stream);
 
+/* ---- the stage-2 transformer's attention, FORWARD only (reference modules/transformer/attention.py:113-124: scaled_dot_product_attention
+ * on jagged NestedTensors; csrc/attention.hip).  q, out [total_q, H * Dh] and k, v [total_kv, H * Dh], fp32, each with its own row stride
+ * in floats (ldq, ldk, ldv, ldo: >= H * Dh, multiples of 4; the pointers 16-byte aligned), so the column-chunk views of a packed
+ * [T, 3 d] qkv or [T, 2 d] kv matrix are taken as they are.  Head h is columns [h Dh, (h + 1) Dh).  q_offsets [nq + 1] and
+ * kv_offsets [nkv + 1]: int64 on the device, exclusive scans of the sequence lengths (q_offsets[nq] = total_q, kv_offsets[nkv] = total_kv).
+ *   kv_group  g >= 1 with nq == nkv * g: query sequence s attends to kv sequence s / g (the beams of one batch item share that item's
+ *             context, which is stored and read once).
+ *   causal    token i of a query sequence sees kv tokens 0 .. i (top-left aligned, as torch); only with kv_group == 1.
+ *   out[r]    = softmax_j(scale * q[r] . k[j]) v[j] per head over the visible j, fp32 accumulation on the fp32 MFMA, online softmax;
+ *             no dropout.  A query sequence of length 0 writes nothing; a row with NO visible kv token (an empty kv sequence) is written
+ *             as zeros (torch gives NaN there; the reference never produces the case).
+ *             Inputs are taken to be finite: a 32-row tile walks the kv rows of ALL its segments and drops the ones a row may not see
+ *             by p = 0, so an Inf or NaN in a k / v row reaches (as NaN) the rows of neighbouring sequences that share its tile.
+ * head_dim in {32, 64, 128}; any num_heads >= 1; total_q, total_kv, nq < 2^31.  The launch shape depends on (total_q, num_heads) alone:
+ * no host read of the offsets, no synchronisation, no workspace, no allocation; capturable in a HIP graph.  Reproducible: one wave
+ * produces an output row, walking its kv tokens in ascending tiles; no atomics. */
+int hidvae_jagged_attention_fwd(const float *q, int64_t ldq, const float *k, int64_t ldk, const float *v, int64_t ldv, float *out,
+                                int64_t ldo, const int64_t *q_offsets, int64_t nq, int64_t total_q, const int64_t *kv_offsets,
+                                int64_t nkv, int64_t total_kv, int num_heads, int head_dim, int kv_group, int causal, float scale,
+                                void *stream);
+
 /* ---- the training loop's batch formation (reference data/tags_processed.py:112-150: ItemData.__getitem__ indexes item_data,
  * tags_emb and tags_indices with the batch's ids; train_hidvae.py:698-701 hands the batch to the step).  ONE launch gathers the rows
  * idx[0 .. rows) of up to HIDVAE_GATHER_MAX resident tables (host arrays of n_tables device pointers: src[t] has src_rows[t] rows of
